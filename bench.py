@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — benchmarks of the MI355X zstd / S2 encode hot path on the BASELINE.json configurations.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C2H|C3|C4|C5] [--gib G] [--kind T|H|J|M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C2H|C3|C4|C5] [--gib G] [--kind T|H|J|M] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step, ratio, the roofline figures taken from
+the timed steps' own kernel timings).  Everything else the benchmark measures or checks runs only with --full: the CPU baseline and the
+byte compare with the oracle, the on-device round trip of every frame, the end-to-end host-buffer rate, roofline.floor, the N > 1
+gather check, and on the default C2 run the other configurations as "also".  --dump-outputs DIR writes what the last timed step
+computed (rank 0's frames: offsets, per-frame checksums and the bytes of a fixed sample of frames) as DIR/<name>.npy.
 
 Default (what the driver runs): C2 = BASELINE.json configs[1], the configuration the headline metric is quoted on:
 zstd SpeedFastest, synthetic enwik-style text 'T' in independent 128 KiB units (each unit == one reference EncodeAll
@@ -72,6 +78,42 @@ def cpu_quota():
     except Exception:
         pass
     return cores, quota
+
+
+DUMP_SAMPLE_FRAMES = 64
+DUMP_SAMPLE_SEED = 0x5EED00D0
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, d_dst, out_off):
+    """--dump-outputs: the frames of the last timed step as .npy files (float64 / float32, < 64 MiB together) —
+    frame_offsets (all n + 1 offsets), frame_checksums (per frame: byte sum and 1-based position-weighted byte sum, exact in
+    float64), frame_sample_units (a fixed seeded sample of frame indices) and frame_sample_bytes (those frames' bytes, concatenated)."""
+    import numpy as np
+    import torch
+    n = len(out_off) - 1
+    off = np.asarray(out_off, dtype=np.int64)
+    sums = np.zeros((n, 2), dtype=np.float64)
+    for a in range(0, n, 256):  # 256 frames at a time bounds the int64 temporaries on the device
+        b = min(n, a + 256)
+        x = d_dst[int(off[a]):int(off[b])].to(torch.int64)
+        sizes = torch.from_numpy(np.diff(off[a:b + 1])).to(x.device)
+        seg = torch.repeat_interleave(torch.arange(b - a, device=x.device), sizes)
+        pos = torch.arange(x.numel(), device=x.device) - torch.from_numpy(off[a:b] - off[a]).to(x.device)[seg] + 1
+        s0 = torch.zeros(b - a, dtype=torch.int64, device=x.device).index_add_(0, seg, x)
+        s1 = torch.zeros(b - a, dtype=torch.int64, device=x.device).index_add_(0, seg, x * pos)
+        sums[a:b, 0] = s0.cpu().numpy()
+        sums[a:b, 1] = s1.cpu().numpy()
+    units = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=min(DUMP_SAMPLE_FRAMES, n), replace=False))
+    sample = torch.cat([d_dst[int(off[u]):int(off[u + 1])] for u in units]).cpu().numpy()
+    arrays = {"frame_offsets": off.astype(np.float64), "frame_checksums": sums,
+              "frame_sample_units": units.astype(np.float64), "frame_sample_bytes": sample.astype(np.float32)}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes of outputs exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def collect_pmc(argv, kernel_key):
@@ -257,7 +299,16 @@ def main():
     ap.add_argument("--path", default="auto", choices=["auto", "hbm", "lds"], help="kernel family of SpeedFastest / s2.Encode (KC_OPT_MATCH_PATH)")
     ap.add_argument("--e2e-calls", type=int, default=4, help="end_to_end steady state: host-buffer calls kept in flight (contexts used with submit / wait)")
     ap.add_argument("--e2e-steps", type=int, default=12, help="end_to_end steady state: batches timed")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baseline + oracle byte compare, on-device round trip, end_to_end, "
+                         "roofline.floor, the N > 1 gather check and (default C2 run) the other configurations as \"also\"; each keeps its --no-* switch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's frames (rank 0) as DIR/<name>.npy: offsets, per-frame checksums, a fixed sample of frame bytes")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the result line
+        args.no_cpu_baseline = args.no_floor = args.no_end_to_end = args.no_device_verify = args.no_also = True
     if args.contexts == 1:
         ap.error("--contexts counts the contexts of the two-stage pipeline (2 or 3); for one context with steps back to back use --no-pipeline")
     if args.pipeline is None:
@@ -324,7 +375,8 @@ def main():
     n_units = int(cfg["gib"] * (1 << 30)) // UNIT
     first_unit = rank * n_units  # contiguous shard per rank keeps output order == concatenation order
     t0 = time.time()
-    host = _lib.corpus_fill(kind, SEEDS[kind], first_unit, n_units, UNIT)
+    cores_, quota_ = cpu_quota()  # (the bytes do not depend on the thread count)
+    host = _lib.corpus_fill(kind, SEEDS[kind], first_unit, n_units, UNIT, threads=min(cores_, quota_ or cores_))
     gen_s = time.time() - t0
     d_src = torch.from_numpy(host).cuda(local_rank)
     unit_off = np.arange(n_units + 1, dtype=np.uint64) * UNIT
@@ -485,12 +537,14 @@ def main():
     ms_per_step = dt * 1000.0 / args.steps
     out_bytes = int(out_off[n_units])
     value = world * in_bytes / (ms_per_step / 1000.0) / 1e6  # MB/s (1e6) of input, whole job
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_dst, out_off)
 
     # ---- N > 1, outside the timed region: the gathered stream IS the ranks' frames in rank order.  Every rank digests the frames of
     # its last step on its own GPU (two wrapping 64-bit sums, one position-weighted), the digests travel in one small all_gather,
     # the last step's frames are gathered once more and rank 0 digests each segment of what arrived ----
     gather_ok = None
-    if gather is not None:
+    if gather is not None and args.full:
         def digest(t):
             """two wrapping 64-bit sums of a byte tensor (one position-weighted) + its length, in 64 MiB pieces (no full-size temporaries)"""
             n = t.numel()
@@ -881,7 +935,7 @@ def main():
                    # (launches of consecutive steps share the chip: 3 steps would be mostly fill and drain)
                    "--steps", str(max(args.also_steps, 9) if name == "C5" else max(args.also_steps, 6) if name == "C3" else max(args.also_steps, 12) if (name.startswith("C4") and "Best" not in name) else args.also_steps),
                    "--warmup", "3" if (name == "C5" or (name.startswith("C4") and "Best" not in name)) else "2" if name == "C3" else "1",
-                   "--no-also", "--cpu-sample-units", "1024" if not extra else "256", "--path", args.path] + extra
+                   "--full", "--no-also", "--cpu-sample-units", "1024" if not extra else "256", "--path", args.path] + extra
             if name not in ("C3", "C4", "C5"):  # the host-buffer rate of every BASELINE configuration; not of the side lines
                 cmd.append("--no-end-to-end")
             if name == "C2/one-context":  # like for like with rounds 1-3 (one context, steps back to back): no second CPU baseline

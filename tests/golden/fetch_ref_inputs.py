@@ -26,10 +26,20 @@ FILES = [
     "testdata/e.txt", "testdata/gettysburg.txt", "testdata/Mark.Twain-Tom.Sawyer.txt", "testdata/sharnd.out",
     "testdata/pi.txt", "testdata/html.txt", "testdata/pngdata.bin",
     "zstd/testdata/z000028",
+    "zstd/testdata/z000028.zst", "zstd/testdata/good.zip", "zstd/testdata/bad.zip", "zstd/testdata/benchdecoder.zip",
+    "zstd/testdata/decode-regression.zip", "zstd/testdata/dict-tests-small.zip",
+    "testdata/crash1.bin", "testdata/crash2.bin", "testdata/crash3.bin", "testdata/endzerobits.bin", "testdata/endnonzero.bin",
+    "testdata/case1.bin", "testdata/case2.bin", "testdata/case3.bin", "testdata/normcount2.bin",
 ]
+# s2's golden Snappy pair: its text differs from testdata/'s file of the same name, so it keeps a folder of its own
+S2_FILES = ["s2/testdata/Mark.Twain-Tom.Sawyer.txt", "s2/testdata/Mark.Twain-Tom.Sawyer.txt.rawsnappy"]
 
 if __name__ == "__main__":
     os.makedirs(DST, exist_ok=True)
     for f in FILES:
         shutil.copyfile(os.path.join(REF, f), os.path.join(DST, os.path.basename(f)))
         print(f, os.path.getsize(os.path.join(DST, os.path.basename(f))))
+    os.makedirs(os.path.join(DST, "s2"), exist_ok=True)
+    for f in S2_FILES:
+        shutil.copyfile(os.path.join(REF, f), os.path.join(DST, "s2", os.path.basename(f)))
+        print(f, os.path.getsize(os.path.join(DST, "s2", os.path.basename(f))))

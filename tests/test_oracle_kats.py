@@ -7,7 +7,8 @@ import os
 import pytest
 
 KATS = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "kats.json")))
-REF = "/root/reference"
+# the reference's own fixtures, committed copies (tests/golden/fetch_ref_inputs.py): one flat folder, s2's golden Snappy pair in s2/
+REF_INPUTS = os.path.join(os.path.dirname(__file__), "golden", "ref_inputs")
 
 
 def test_xxh64_kats(oracle):
@@ -82,26 +83,24 @@ def test_s2_max_encoded_len_kat(oracle, kclib):
         assert L.kco_s2_max_encoded_len(i) == i + varint + extra == kclib.kc_s2_max_encoded_len(i)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present on this machine")
 def test_frame_boundaries_on_reference_fixtures(oracle):
     """C1: EncodeAll(e.txt) at SpeedFastest starts 28 B5 2F FD A4 A3 86 01 00 and ends 5F 0C 04 7D."""
     enc = oracle.ZstdOracle(level=1)
     for name, g in KATS["files"].items():
         if "frame_prefix" not in g:
             continue
-        data = open(os.path.join(REF, "testdata", name), "rb").read()
+        data = open(os.path.join(REF_INPUTS, name), "rb").read()
         assert hashlib.sha256(data).hexdigest() == g["sha256"]
         out = enc.encode_all(data)
         assert out.hex().startswith(g["frame_prefix"]), name
         assert out[-4:].hex() == g["frame_suffix"], name
         assert oracle.lib().kco_xxh64(data, len(data)) == int(g["xxh64"], 16)
         assert oracle.zstd_decompress(out, len(data) + 16) == data
-    e = open(os.path.join(REF, "testdata", "e.txt"), "rb").read()
+    e = open(os.path.join(REF_INPUTS, "e.txt"), "rb").read()
     out = enc.encode_all(e)
     assert out[:9].hex() == "28b52ffda4a3860100" and out[-4:].hex() == "5f0c047d"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present on this machine")
 @pytest.mark.parametrize("level", [1, 2, 3])
 def test_reference_corpora_roundtrip(oracle, level):
     """The reference's encoder tests are round-trip tests (zstd/encoder_test.go:68-160, fuzz_test.go:154):
@@ -111,7 +110,7 @@ def test_reference_corpora_roundtrip(oracle, level):
     enc = oracle.ZstdOracle(level=level)
     n = 0
     for zf in ("zstd/testdata/fuzz/encode-corpus-raw.zip", "zstd/testdata/comp-crashers.zip"):
-        z = zipfile.ZipFile(os.path.join(REF, zf))
+        z = zipfile.ZipFile(os.path.join(REF_INPUTS, os.path.basename(zf)))
         for k, name in enumerate(z.namelist()):
             d = z.read(name)
             out = enc.encode_all(d)
@@ -282,7 +281,6 @@ def test_in_repo_decoder_on_c_zstd_frames(oracle):
             oracle.zstd_decode(bad, 1 << 22, dict_blob=blob)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present on this machine")
 def test_in_repo_decoder_on_reference_regression_frames(oracle):
     """The reference's decoder test inputs (zstd/testdata/good.zip, benchdecoder.zip: C-zstd frames at many levels, skippable
     frames, multi-frame files): wherever libzstd decodes a file, the in-repo decoder must produce the same bytes."""
@@ -293,7 +291,7 @@ def test_in_repo_decoder_on_reference_regression_frames(oracle):
         pytest.skip("no system libzstd to compare with")
     checked = 0
     for name in ("good.zip", "benchdecoder.zip"):
-        zf = zipfile.ZipFile(os.path.join(REF, "zstd", "testdata", name))
+        zf = zipfile.ZipFile(os.path.join(REF_INPUTS, name))
         for n in zf.namelist()[:400]:
             z = zf.read(n)
             if len(z) < 6 or len(z) > 300000:
@@ -412,7 +410,6 @@ _FSE_TABLE = [  # fse/fse_test.go:19-50: (name, input, err)
     ("case1", "case1.bin", 1), ("case2", "case2.bin", 1), ("case3", "case3.bin", 1), ("pngdata.001", "pngdata.bin", 0), ("normcount2", "normcount2.bin", 0)]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present on this machine")
 def test_huff0_and_fse_outcome_tables(oracle):
     """The reference's own expectation tables for huff0.Compress1X / Compress4X (huff0/compress_test.go:20-52,
     TestCompress1X :225, TestCompress4X :361) and fse.Compress (fse/fse_test.go:19-50, TestCompress :68): which inputs
@@ -420,7 +417,7 @@ def test_huff0_and_fse_outcome_tables(oracle):
     L = oracle.lib()
 
     def load(x):
-        return x if isinstance(x, bytes) else open(os.path.join(REF, "testdata", x), "rb").read()
+        return x if isinstance(x, bytes) else open(os.path.join(REF_INPUTS, x), "rb").read()
 
     for name, src, e1, e4 in _HUF_TABLE:
         d = load(src)[:(1 << 18) - 1]
@@ -457,10 +454,9 @@ def test_s2_encode_better_roundtrip_and_gain(oracle):
     assert len(oracle.s2_encode_better(h)) == len(h) + 3 + 3  # incompressible: uvarint(3) + one literal (tag 61<<2 + 2 length bytes)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference fixtures not present on this machine")
 def test_s2_encode_better_reference_regressions_roundtrip(oracle):
     import zipfile
-    z = zipfile.ZipFile(os.path.join(REF, "s2/testdata/enc_regressions.zip"))
+    z = zipfile.ZipFile(os.path.join(REF_INPUTS, "enc_regressions.zip"))
     n = 0
     for name in z.namelist():
         d = z.read(name)
@@ -512,10 +508,9 @@ def test_s2_encode_snappy_is_snappy_and_roundtrips(oracle):
     """s2.EncodeSnappy restatement: a strict Snappy decoder (no S2 extensions) reads the blocks; the reference's golden
     Snappy file (s2/testdata/Mark.Twain-Tom.Sawyer.txt.rawsnappy, s2_test.go:595-615) checks that decoder."""
     import corpora
-    gold_dir = os.path.join(REF, "s2", "testdata")
-    if os.path.isdir(gold_dir):
-        want = open(os.path.join(gold_dir, "Mark.Twain-Tom.Sawyer.txt"), "rb").read()
-        assert _snappy_decode_strict(open(os.path.join(gold_dir, "Mark.Twain-Tom.Sawyer.txt.rawsnappy"), "rb").read()) == want
+    gold_dir = os.path.join(REF_INPUTS, "s2")
+    want = open(os.path.join(gold_dir, "Mark.Twain-Tom.Sawyer.txt"), "rb").read()
+    assert _snappy_decode_strict(open(os.path.join(gold_dir, "Mark.Twain-Tom.Sawyer.txt.rawsnappy"), "rb").read()) == want
     for kind in "TJMH":
         for n in (65536, 65537, 300000):
             d = corpora.corpus(kind, 1, n).tobytes()

@@ -4,7 +4,7 @@ reference" is that translator and its runtime (gort.h).  The reference ships dec
 strings for its S2 emitters; its own translated DECODER and EMITTERS — the same front end, the same runtime: typed wrap-around
 integers, slices, shifts — must reproduce them, in all three builds of the decoder (portable Go; amd64 with its assembly, BMI2 on and
 off).  zstd/decoder_test.go (testDecoderFile / testDecoderDecodeAll / testDecoderFileBad fixture loops), zstd/dict_test.go:16-100,
-s2/s2_test.go:37-76, 827-942.  CPU only; skipped where /root/reference (and with it the built library) is absent."""
+s2/s2_test.go:37-76, 827-942.  CPU only; skipped where the built library (oracle/_ref) is absent."""
 import glob
 import io
 import json
@@ -15,10 +15,10 @@ import pytest
 
 import oracle_goref as G
 
-REF = "/root/reference"
-TD = os.path.join(REF, "zstd", "testdata")
+# the reference's own fixtures, committed copies (tests/golden/fetch_ref_inputs.py)
+TD = os.path.join(os.path.dirname(__file__), "golden", "ref_inputs")
 KATS = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "kats.json")))
-pytestmark = pytest.mark.skipif(not (os.path.isdir(TD) and G.available()), reason="reference fixtures / oracle/_ref not present on this machine")
+pytestmark = pytest.mark.skipif(not G.available(), reason="oracle/_ref not present on this machine")
 
 
 def _flavours():
@@ -188,7 +188,7 @@ def test_translated_max_encoded_len_gives_the_reference_vectors():
 def test_translated_s2_decode_on_the_reference_golden_snappy_block(oracle):
     """TestDecodeGoldenInput (s2/s2_test.go:598-614): Mark.Twain-Tom.Sawyer.txt.rawsnappy -> Mark.Twain-Tom.Sawyer.txt through the
     reference's own s2.Decode, translated; and the block encoders' round trip through it on that text at all six levels."""
-    td = os.path.join(REF, "s2", "testdata")
+    td = os.path.join(TD, "s2")
     want = open(os.path.join(td, "Mark.Twain-Tom.Sawyer.txt"), "rb").read()
     assert G.s2_decode(open(os.path.join(td, "Mark.Twain-Tom.Sawyer.txt.rawsnappy"), "rb").read(), len(want)) == want
     for level in range(6):

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/bench_$TAG
 mkdir -p $OUT
 for c in C2 C2H C3 C4 C5; do
-  python bench.py --config $c --steps $STEPS --warmup 1 > $OUT/$c.json 2> $OUT/$c.err
+  python bench.py --config $c --steps $STEPS --warmup 1 --full > $OUT/$c.json 2> $OUT/$c.err
   tail -c 2200 $OUT/$c.json | python -c "
 import sys, json
 try:

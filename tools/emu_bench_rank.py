@@ -5,7 +5,7 @@ frames overlapped with the next step, barrier + MAX timing, dictionary broadcast
 TEST INFRASTRUCTURE; launched by tools/emu_bench_flow.sh-style commands:
 
     KC_LIB_TAG=emu PYTHONPATH=tools python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 tools/emu_bench_rank.py \
-        --gpus 2 --gib 0.001953125 --steps 3 --warmup 1 --no-also --no-cpu-baseline
+        --gpus 2 --gib 0.001953125 --steps 3 --warmup 1 --full --no-also --no-cpu-baseline
 """
 import os
 import runpy

@@ -8,13 +8,13 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd $R
-# 1. the default command, as the driver runs it (C2, 10 steps)
-python bench.py > $OUT/bench_C2.json 2> $OUT/bench_C2.err
+# 1. the default command with everything it measures (C2, 10 steps, the other configurations as "also")
+python bench.py --full > $OUT/bench_C2.json 2> $OUT/bench_C2.err
 # 2. kernel-trace stats of the same command
 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/kt_C2 -- python bench.py --no-also --no-cpu-baseline --no-end-to-end > $OUT/kt_C2.log 2>&1
 # 3. the other configurations: bench line + kernel-trace stats
 for c in C2H C3 C4 C4A C5 B4; do
-  python bench.py --config $c --steps 5 --warmup 1 > $OUT/bench_$c.json 2> $OUT/bench_$c.err
+  python bench.py --config $c --steps 5 --warmup 1 --full > $OUT/bench_$c.json 2> $OUT/bench_$c.err
   timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/kt_$c -- python bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end --no-device-verify > $OUT/kt_$c.log 2>&1
 done
 # 3b. the LDS-table kernels at small batches (one wave per unit): kernel-trace stats of the crossover sweep up to 256 units

@@ -31,8 +31,8 @@ doc["entries"] = [ent[k] for k in ("C2", "C3", "C4", "C5") if k in ent]
 json.dump(doc, open(p, "w"), indent=1)
 json.dump(doc, open(os.path.join(out, "pmc_traffic.json"), "w"), indent=1)
 PY
-python bench.py > $OUT/bench_C2.json 2> $OUT/bench_C2.err
+python bench.py --full > $OUT/bench_C2.json 2> $OUT/bench_C2.err
 for c in C2H C3 C4 C5; do
-  python bench.py --config $c --steps 5 --warmup 1 > $OUT/bench_$c.json 2> $OUT/bench_$c.err
+  python bench.py --config $c --steps 5 --warmup 1 --full > $OUT/bench_$c.json 2> $OUT/bench_$c.err
 done
 for c in C2 C2H C3 C4 C5; do tail -1 $OUT/bench_$c.json | cut -c1-300; done

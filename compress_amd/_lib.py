@@ -7,6 +7,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libkcgpu%s.so" % ("_" + os.environ["KC_LIB_TAG"] if os.environ.get("KC_LIB_TAG") else ""))
 
 KC_OK = 0
+# per-input status classes of zstd.Decoder.DecodeAll (include/kcgpu.h KC_ZD_*)
+ZD_NAMES = {0: "KC_ZD_OK", 1: "KC_ZD_MAGIC", 2: "KC_ZD_EOF", 3: "KC_ZD_UNKNOWN_DICT", 4: "KC_ZD_WINDOW_EXCEEDED", 5: "KC_ZD_SIZE_EXCEEDED",
+            6: "KC_ZD_CRC", 7: "KC_ZD_CORRUPT"}
 KC_ERR_BAD_ARG, KC_ERR_DST_TOO_SMALL, KC_ERR_HIP, KC_ERR_UNSUPPORTED, KC_ERR_NO_DEVICE, KC_ERR_INTERNAL = -1, -2, -3, -4, -5, -6
 _NAMES = {0: "KC_OK", -1: "KC_ERR_BAD_ARG", -2: "KC_ERR_DST_TOO_SMALL", -3: "KC_ERR_HIP", -4: "KC_ERR_UNSUPPORTED",
           -5: "KC_ERR_NO_DEVICE", -6: "KC_ERR_INTERNAL"}
@@ -42,6 +45,8 @@ SYMBOLS = [
     "kc_zstd_encode_units", "kc_zstd_encode_units_dev", "kc_zstd_encode_streams_dev", "kc_zstd_encode_streams", "kc_zstd_encode_streams_cuts_dev", "kc_zstd_encode_streams_cuts", "kc_zstd_encode_units_submit", "kc_s2_encode_blocks_lvl_submit", "kc_wait", "kc_zstd_plan_stream_blocks", "kc_zstd_encode_units_dev_begin", "kc_zstd_encode_units_dev_end", "kc_zstd_encode_units_dev_end_at", "kc_ctx_chain_after", "kc_xxh64_units_dev", "kc_zstd_debug_parse_dev",
     "kc_s2_max_encoded_len", "kc_s2_encode_blocks", "kc_s2_encode_blocks_dev", "kc_s2_encode_stream_dev", "kc_s2_decode_blocks_dev", "kc_zstd_decode_units_dev", "kc_zstd_decode_units_dict_dev", "kc_s2_encode_block", "kc_s2_hook_stats", "kc_s2_encode_blocks_lvl", "kc_s2_encode_blocks_lvl_dev", "kc_s2_encode_blocks_lvl_dev_begin", "kc_s2_encode_blocks_lvl_dev_end_at", "kc_s2_encode_stream_lvl_dev",
     "kc_last_timings", "kc_corpus_fill", "kc_ctx_set_option", "kc_ctx_get_option", "kc_zstd_encode_jobs", "kc_zstd_job_size", "kc_zstd_overlap_size",
+    "kc_zstd_dopts_default", "kc_zstd_dopts_free", "kc_zstd_dopts_max_memory", "kc_zstd_dopts_max_window", "kc_zstd_dopts_ignore_checksum", "kc_zstd_dopts_dict", "kc_zstd_dopts_dict_raw",
+    "kc_zstd_decode_all_dev", "kc_zstd_decode_all", "kc_zstd_decode_all_bound_dev", "kc_zstd_decode_all_bound",
     "kc_probe_table_pattern", "kc_probe_pcie", "kc_ctx_trim", "kc_device_trim", "kc_s2_hook_declined", "kc_create_error", "kc_host_alloc", "kc_host_free",
 ]
 
@@ -153,6 +158,28 @@ def load():
     L.kc_zstd_decode_units_dict_dev.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, u64]
     L.kc_zstd_decode_units_dict_dev.restype = C.c_int
     L.kc_s2_decode_blocks_dev.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp]
+    L.kc_zstd_dopts_default.argtypes = []
+    L.kc_zstd_dopts_default.restype = vp
+    L.kc_zstd_dopts_free.argtypes = [vp]
+    L.kc_zstd_dopts_free.restype = None
+    for n in ("max_memory", "max_window"):
+        f = getattr(L, "kc_zstd_dopts_" + n)
+        f.argtypes = [vp, u64]
+        f.restype = C.c_int
+    L.kc_zstd_dopts_ignore_checksum.argtypes = [vp, C.c_int]
+    L.kc_zstd_dopts_ignore_checksum.restype = C.c_int
+    L.kc_zstd_dopts_dict.argtypes = [vp, vp, u64]
+    L.kc_zstd_dopts_dict.restype = C.c_int
+    L.kc_zstd_dopts_dict_raw.argtypes = [vp, C.c_uint32, vp, u64]
+    L.kc_zstd_dopts_dict_raw.restype = C.c_int
+    for n in ("kc_zstd_decode_all_dev", "kc_zstd_decode_all"):
+        f = getattr(L, n)
+        f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, u64, vp, vp]
+        f.restype = C.c_int
+    for n in ("kc_zstd_decode_all_bound_dev", "kc_zstd_decode_all_bound"):
+        f = getattr(L, n)
+        f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp]
+        f.restype = C.c_int
     L.kc_s2_decode_blocks_dev.restype = C.c_int
     L.kc_s2_encode_block.argtypes = [vp, vp, u64, vp, u64]
     L.kc_s2_encode_block.restype = C.c_int64

@@ -5,12 +5,16 @@
 // repeat offsets (enc_base.go:189-195) and the content (initial history).  The three FSE tables of the dictionary
 // are only consumed by decoders; they are parsed here to find where they end and to reject malformed input.
 //
+// kc_dict_load_decoder (below) is the DECODER's view of the same blob (WithDecoderDicts): the Huffman decoding table and the three
+// FSE decoding tables in the layout of the decode kernel (kc_zstd_decode_all.hip), built once when the dictionary is registered.
+//
 // Written against the Zstandard format description (Dictionary_Format, Huffman_Tree_Description, FSE_Table_Description)
 // with a forward bit cursor for table descriptions and a backward one for the FSE-compressed weights.
 #include <stdint.h>
 #include <string.h>
 
 #include "../../include/kcgpu.h"
+#include "kc_kernels.h"
 
 namespace {
 
@@ -227,5 +231,54 @@ extern "C" int kc_zstd_opts_dict(kc_zstd_opts* o, const uint8_t* blob, uint64_t 
     o->dict_id = id;
     o->dict = p;
     o->dict_len = n;
+    return 0;
+}
+
+// WithDecoderDicts: what a decoder takes from a full-format dictionary (zstd/dict.go:71-150, history.setDict): ID, content, the three
+// repeat offsets, and the literal Huffman table and the offset / match-length / literal-length FSE tables as the "previous" tables of
+// a frame's first block — as decoding tables in the layout of KcZdDict.  *content points into `blob`.  Returns 0, or -1 when the
+// reference's loadDict would return an error (the same verdict as kc_zstd_opts_dict, which does the checking).
+int kc_dict_load_decoder(const uint8_t* blob, uint64_t len, KcZdDict* D, const uint8_t** content, uint64_t* content_len) {
+    kc_zstd_opts o;
+    memset(&o, 0, sizeof(o));
+    if (D == nullptr || kc_zstd_opts_dict(&o, blob, len) != 0) return -1;
+    memset(D, 0, sizeof(*D));
+    D->id = o.dict_id;
+    D->full = 1;
+    for (int k = 0; k < 3; k++) D->rep[k] = o.dict_offsets[k];
+    *content = o.dict;
+    *content_len = o.dict_len;
+    D->content_len = (uint32_t)o.dict_len;
+    // Huffman decoding cells, ordered by (weight ascending, symbol ascending); a symbol of weight w has 2^(w-1) of them
+    const int tl = o.dict_huf_log;
+    D->huf_log = tl;
+    uint32_t pos = 0;
+    for (int w = 1; w <= tl; w++)
+        for (int s = 0; s < o.dict_huf_len; s++) {
+            const int nb = o.dict_huf_nbits[s];
+            if (nb == 0 || tl + 1 - nb != w) continue;
+            for (uint32_t k = 0; k < (1u << (w - 1)); k++) D->huf[pos + k] = (uint16_t)((s << 8) | nb);
+            pos += 1u << (w - 1);
+        }
+    if (pos != (1u << tl)) return -1;
+    // the three FSE tables behind the Huffman description, in the blob's order: offsets, match lengths, literal lengths
+    const uint8_t* p = blob + 8;
+    size_t n = (size_t)len - 8;
+    const size_t hsz = p[0] >= 128 ? 1 + (size_t)((p[0] - 127) + 1) / 2 : 1 + (size_t)p[0];
+    p += hsz; n -= hsz;
+    const int maxSyms[3] = {30, 52, 35};
+    KcZdCell* dst[3] = {D->of, D->ml, D->ll};
+    int32_t* logs[3] = {&D->of_log, &D->ml_log, &D->ll_log};
+    for (int t = 0; t < 3; t++) {
+        int16_t norm[256];
+        int ns = 0, tlog = 0;
+        const size_t used = read_ncount(p, n, maxSyms[t], 9, norm, &ns, &tlog);
+        if (used == 0 || used > n || tlog > (t == 0 ? 8 : 9)) return -1;
+        static thread_local DState dt[1 << 9];
+        if (!build_dtable(norm, ns, tlog, dt)) return -1;
+        for (int u = 0; u < (1 << tlog); u++) { dst[t][u].base = dt[u].base; dst[t][u].sym = dt[u].sym; dst[t][u].nb = dt[u].nb; }
+        *logs[t] = tlog;
+        p += used; n -= used;
+    }
     return 0;
 }

@@ -1,7 +1,8 @@
 #pragma once
 // kc_host.h — internal header of the host side of the C ABI (include/kcgpu.h): the context, its scratch buffers and the batch
 // records shared by the translation units kc_ctx.cpp (options, context), kc_batch.cpp (the zstd device pipeline), kc_zstd_host.cpp
-// (host-buffer entry points), kc_jobs.cpp (WithConcurrentBlocks), kc_s2_api.cpp (S2) and kc_hook.cpp (the WriterCustomEncoder hook).
+// (host-buffer entry points), kc_jobs.cpp (WithConcurrentBlocks), kc_s2_api.cpp (S2), kc_zstd_dec_api.cpp (DecodeAll) and kc_hook.cpp
+// (the WriterCustomEncoder hook).
 // Not installed: the boundary is include/kcgpu.h.
 // There is deliberately NO CPU fallback in this library: when the device path cannot serve a
 // request it returns KC_ERR_UNSUPPORTED / KC_ERR_NO_DEVICE and the caller (the Go shim)
@@ -170,6 +171,7 @@ struct kc_ctx {
     const uint8_t* job_tables = nullptr;    // host or null: the units' tables primed from their prefixes (ResetPrefix), device entry format
     bool job_primed = false;                // the units' tables start primed from their prefixes: by kc_zstd_prime_kernel, or from job_tables
     DevBuf d_job_hist, d_job_flags, rawdef, unit_raw;
+    DevBuf zd[20];                       // zstd.Decoder.DecodeAll (kc_zstd_dec_api.cpp): plan, frame records, staging, literal scratch
     DevBuf unit_done, probe_rel;         // no-match pre-scan (kc_zstd_prescan.hip): per-unit verdicts; the probe positions of one block
     int probe_bs = 0;                    // block size probe_rel was built for
     uint32_t probe_n = 0;
@@ -277,3 +279,5 @@ kc_status host_rolling(kc_ctx* c, const uint8_t* src, const uint64_t* unit_off, 
 uint64_t host_roll_sub_bytes(const kc_ctx* c, uint64_t total);
 kc_status host_roll_trim(int device);  // kc_device_trim: free the idle engine's device slots and its lanes' scratch
 }  // namespace kci
+// kc_dict.cpp: the decoder's view of a full-format dictionary (WithDecoderDicts)
+int kc_dict_load_decoder(const uint8_t* blob, uint64_t len, KcZdDict* D, const uint8_t** content, uint64_t* content_len);

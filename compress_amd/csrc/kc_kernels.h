@@ -224,6 +224,71 @@ struct KcZstdDecParams {
     uint32_t dict_len;
 };
 void kc_launch_zstd_decode(const KcZstdDecParams& P, hipStream_t st);
+// ---- zstd.Decoder.DecodeAll as a product (kc_zstd_plan.hip, kc_zstd_decode_all.hip; host side kc_zstd_dec_api.cpp) ----
+// Per-input / per-frame status classes (include/kcgpu.h KC_ZD_*)
+enum { KCZD_OK = 0, KCZD_MAGIC = 1, KCZD_EOF = 2, KCZD_UNKNOWN_DICT = 3, KCZD_WINDOW = 4, KCZD_SIZE = 5, KCZD_CRC = 6, KCZD_CORRUPT = 7 };
+#define KC_ZD_NO_SIZE 0xFFFFFFFFFFFFFFFFull       // a frame without Frame_Content_Size
+#define KC_ZD_MAX_FRAME 0xFFFFFF00ull             // largest decoded frame the device path serves (sizes of the compaction are 32-bit)
+#define KC_ZD_LIT_STRIDE ((128u << 10) + 64u)     // literal scratch per frame: one block's regenerated literals
+struct KcZdCell { uint16_t base; uint8_t sym; uint8_t nb; };  // FSE decoding cell (the layout of ZdSym, kc_zdec_dev.h)
+// One registered dictionary as the decode kernel reads it.  Full-format dictionaries (full = 1) carry the tables a frame's first
+// block may use in "repeat" / "treeless" mode and their own repeat offsets (zstd/dict.go, history.setDict); raw ones {1, 4, 8}.
+struct KcZdDict {
+    uint32_t id, content_len;
+    uint64_t content_off;        // where the content starts in the dictionary arena
+    uint32_t rep[3];
+    uint32_t full;
+    int32_t huf_log, ll_log, of_log, ml_log;
+    uint16_t huf[1 << 11];       // symbol << 8 | nBits, index = next huf_log bits
+    KcZdCell ll[1 << 9], of[1 << 8], ml[1 << 9];
+};
+// One frame of one input, written by the plan kernel and consumed by the decode kernel.
+struct KcZdFrame {
+    uint64_t blk_begin, blk_end; // positions in src: the first block header .. behind the last block (the checksum, if any, follows)
+    uint64_t window;
+    uint64_t fcs;                // Frame_Content_Size or KC_ZD_NO_SIZE
+    uint64_t slot_off;           // where the frame decodes to in the staging area (16-byte aligned)
+    uint32_t slot_cap;           // bytes it may write there: fcs, or the bound from the block headers (capped by the size limit)
+    uint32_t dict;               // index + 1 into the dictionaries, 0: none
+    uint32_t checksum;           // 1: four bytes of XXH64 behind blk_end
+    uint32_t input;
+};
+struct KcZdPlanParams {
+    const uint8_t* src;
+    const uint64_t* in_off;      // device, n + 1
+    uint32_t n;
+    uint64_t max_memory, max_window;
+    const KcZdDict* dicts;       // device or null
+    uint32_t n_dicts;
+    // first pass (frames == null): per input the number of frames, the decoded size (exact when every frame carries one, else an
+    // upper bound), the bytes of staging its frames take and the first header-level error
+    uint32_t* n_frames;
+    uint64_t* bound;
+    uint64_t* slot_bytes;
+    uint32_t* exact;
+    uint32_t* status;
+    // second pass: the same walk writes the frame records of the inputs without an error
+    const uint32_t* frame0;      // device, per input: index of its first record
+    const uint64_t* slot0;       // device, per input: where its staging starts
+    KcZdFrame* frames;
+};
+void kc_launch_zstd_plan(const KcZdPlanParams& P, hipStream_t st);
+struct KcZdDecodeParams {
+    const uint8_t* src;
+    const KcZdFrame* frames;
+    uint32_t n_frames;
+    uint8_t* stage;              // the frames' slots
+    uint8_t* lits;               // KC_ZD_LIT_STRIDE bytes per frame
+    const KcZdDict* dicts;
+    const uint8_t* dict_arena;
+    uint64_t max_memory;
+    uint32_t* out_size;          // per frame: bytes decoded (0 on error)
+    uint32_t* status;            // per frame: KCZD_*
+    uint32_t* crc_stored;        // per frame: the stored checksum (frames with one)
+    uint64_t* hash_off;          // 2 * n_frames + 1: [2f] = slot_off, [2f + 1] = slot_off + out_size — kc_launch_xxh64 over these "units"
+                                 // hashes every frame's decoded bytes at the even indices
+};
+void kc_launch_zstd_decode_all(const KcZdDecodeParams& P, hipStream_t st);
 // default: 2^14 entries; better: long 2^17 + short 2^14 (blocks > 64 KiB), long 2^16 + short 2^13 (all blocks <= 64 KiB)
 static inline size_t kc_s2_table_bytes(int level, uint64_t max_block_len, int variant = 0) {
     // the assembly forms of the better levels take 2^17 + 2^14 entries from 16 KiB on (Snappy-compatible: above 64 KiB; 2^16 + 2^13 below)

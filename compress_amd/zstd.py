@@ -1,11 +1,14 @@
-"""Host mirror of the reference's zstd encoder API for the EncodeAll hot path.
+"""Host mirror of the reference's zstd encoder API for the EncodeAll hot path, and of its decoder's DecodeAll.
 
-Names, argument meaning and error behaviour follow zstd/encoder.go and
-zstd/encoder_options.go; the bytes come from the HIP engine behind include/kcgpu.h.
+Names, argument meaning and error behaviour follow zstd/encoder.go, zstd/encoder_options.go, zstd/decoder.go and
+zstd/decoder_options.go; the bytes come from the HIP engine behind include/kcgpu.h.
 
     enc = zstd.NewWriter(None, zstd.WithEncoderLevel(zstd.SpeedFastest))
     frame = enc.EncodeAll(src, b"")                     # == reference EncodeAll(src, nil)
     frames, off = enc.EncodeUnits(buf, unit_off)        # N independent EncodeAll calls, one launch
+    dec = zstd.NewReader(None)
+    plain = dec.DecodeAll(frame, b"")                   # == reference DecodeAll(frame, nil)
+    out, out_off, status = dec.DecodeUnits(frames, off) # N independent DecodeAll calls, one batch
 """
 import contextlib
 import ctypes as C
@@ -553,3 +556,183 @@ class Encoder:
 def NewWriter(w, *opts, **kw):
     """zstd.NewWriter(w, opts...) (encoder.go:71).  w (may be None for block-API use) receives the stream on Close."""
     return Encoder(*opts, w=w, **kw)
+
+
+# ---- zstd.Decoder: DecodeAll over batches on the device (zstd/decoder.go:319-410, decoder_options.go) ----
+class DecodeError(ValueError):
+    """DecodeAll refused its input.  `name` is the class of the reference's error: KC_ZD_MAGIC (ErrMagicMismatch), KC_ZD_EOF
+    (unexpected EOF), KC_ZD_UNKNOWN_DICT, KC_ZD_WINDOW_EXCEEDED, KC_ZD_SIZE_EXCEEDED, KC_ZD_CRC, KC_ZD_CORRUPT (everything else)."""
+
+    def __init__(self, status):
+        self.status = int(status)
+        self.name = _lib.ZD_NAMES.get(self.status, str(self.status))
+        super().__init__("zstd: DecodeAll: %s" % self.name)
+
+
+def _dopt(name, *args):
+    def apply(d):
+        if getattr(_lib.load(), "kc_zstd_dopts_" + name)(d._o, *args) != 0:
+            raise ValueError("zstd decoder option %s rejected" % name)
+    return apply
+
+
+def WithDecoderMaxMemory(n):
+    """zstd.WithDecoderMaxMemory (decoder_options.go:90-101): the most one DecodeAll may return (default 64 GiB)."""
+    return _dopt("max_memory", int(n))
+
+
+def WithDecoderMaxWindow(size):
+    """zstd.WithDecoderMaxWindow (decoder_options.go:150-161; default 512 MiB)."""
+    return _dopt("max_window", int(size))
+
+
+def IgnoreChecksum(b):
+    """zstd.IgnoreChecksum: the content checksum of a frame is skipped, not checked."""
+    return _dopt("ignore_checksum", int(bool(b)))
+
+
+def WithDecoderDicts(*dicts):
+    """zstd.WithDecoderDicts (decoder_options.go:112-126): dictionaries in the `zstd --train` format; a frame's dictionary id picks one."""
+    blobs = [bytes(b) for b in dicts]
+
+    def apply(d):
+        L = _lib.load()
+        for b in blobs:
+            if L.kc_zstd_dopts_dict(d._o, b, len(b)) != 0:
+                raise ValueError("dictionary rejected (loadDict error)")
+    return apply
+
+
+def WithDecoderDictRaw(id, content):
+    """zstd.WithDecoderDictRaw (decoder_options.go:131-142): arbitrary content as the dictionary with this id."""
+    content = bytes(content)
+    return _dopt("dict_raw", int(id), content, len(content))
+
+
+def WithDecoderConcurrency(n):
+    """zstd.WithDecoderConcurrency (decoder_options.go:68-83).  The device path is batch-parallel: no effect on bytes."""
+    if n < 0:
+        raise ValueError("concurrency must be at least 0")
+    return lambda d: None
+
+
+def WithDecoderLowmem(b):
+    """zstd.WithDecoderLowmem: no effect on bytes."""
+    return lambda d: None
+
+
+class Decoder:
+    """zstd.Decoder for the stateless form: DecodeAll, and its batched forms DecodeUnits (host buffers) and DecodeAllDevice
+    (device-resident).  An input is what DecodeAll takes: any concatenation of frames and skippable frames; no decoded size is
+    needed.  The streaming reader (Read / WriteTo over an io.Reader) is not served by the device path."""
+
+    def __init__(self, *opts, device=0, stream=None):
+        L = _lib.load()
+        self._o = C.c_void_p(L.kc_zstd_dopts_default())
+        if not self._o:
+            raise MemoryError("kc_zstd_dopts_default")
+        for op in opts:
+            op(self)
+        self._device, self._stream = device, stream
+        self._ctx = None
+
+    def ctx(self):
+        if self._ctx is None:
+            self._ctx = _lib.Context(self._device, self._stream)
+        return self._ctx
+
+    def DecodeAll(self, input, dst=b""):
+        """Decode all of `input` and append to dst (zstd/decoder.go:319).  Raises DecodeError with the class of the reference's error."""
+        import numpy as np
+        input = bytes(input)
+        out, out_off, status = self.DecodeUnits(np.frombuffer(input, dtype=np.uint8), np.array([0, len(input)], dtype=np.uint64))
+        if status[0]:
+            raise DecodeError(status[0])
+        return bytes(dst) + out.tobytes()
+
+    def DecodeBounds(self, src, in_off):
+        """The plan alone (kc_zstd_decode_all_bound): per input the decoded size — exact when every frame carries its content size,
+        else an upper bound from the block headers — and the first header-level error.  Returns (uint64[n], uint32[n])."""
+        import numpy as np
+        ctx = self.ctx()
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = len(in_off) - 1
+        bound = np.zeros(max(n, 1), dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        if len(src) == 0:
+            src = np.zeros(1, dtype=np.uint8)
+        ctx.check(ctx.L.kc_zstd_decode_all_bound(ctx.h, self._o, src.ctypes.data, in_off.ctypes.data, n, bound.ctypes.data, status.ctypes.data))
+        return bound[:n], status[:n]
+
+    def DecodeUnits(self, src, in_off):
+        """N x DecodeAll(input_i, nil) in one batch.  src: numpy uint8 (host), in_off: uint64[n+1].  Returns (numpy uint8 output,
+        uint64[n+1] offsets, uint32[n] status); an input that fails has a non-zero status (_lib.ZD_NAMES) and an empty range."""
+        import numpy as np
+        ctx = self.ctx()
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = len(in_off) - 1
+        bound, st0 = self.DecodeBounds(src, in_off)
+        cap = int(sum(int(b) for b, s in zip(bound, st0) if s == 0))
+        dst = np.empty(cap + 64, dtype=np.uint8)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        if len(src) == 0:
+            src = np.zeros(1, dtype=np.uint8)
+        ctx.check(ctx.L.kc_zstd_decode_all(ctx.h, self._o, src.ctypes.data, in_off.ctypes.data, n, dst.ctypes.data, cap, out_off.ctypes.data,
+                                           status.ctypes.data))
+        return dst[:int(out_off[n])], out_off, status[:n]
+
+    def DecodeBoundsDevice(self, d_src_ptr, in_off):
+        """DecodeBounds over device-resident inputs (kc_zstd_decode_all_bound_dev): what d_dst must hold."""
+        import numpy as np
+        ctx = self.ctx()
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = len(in_off) - 1
+        bound = np.zeros(max(n, 1), dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        ctx.check(ctx.L.kc_zstd_decode_all_bound_dev(ctx.h, self._o, d_src_ptr, in_off.ctypes.data, n, bound.ctypes.data, status.ctypes.data))
+        return bound[:n], status[:n]
+
+    def DecodeAllDevice(self, d_src_ptr, in_off, d_dst_ptr, dst_cap):
+        """Device-resident form (pointers are ints): returns (uint64[n+1] offsets, uint32[n] status), host numpy.  Raises KcError
+        KC_ERR_DST_TOO_SMALL when the decoded inputs do not fit dst_cap (nothing is written past it)."""
+        import numpy as np
+        ctx = self.ctx()
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = len(in_off) - 1
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        ctx.check(ctx.L.kc_zstd_decode_all_dev(ctx.h, self._o, d_src_ptr, in_off.ctypes.data, n, d_dst_ptr, int(dst_cap), out_off.ctypes.data,
+                                               status.ctypes.data))
+        return out_off, status[:n]
+
+    def Read(self, p):
+        raise NotImplementedError("the streaming reader is not served by the device path: use DecodeAll / DecodeUnits")
+
+    def WriteTo(self, w):
+        raise NotImplementedError("the streaming reader is not served by the device path: use DecodeAll / DecodeUnits")
+
+    def Close(self):
+        """Decoder.Close: the device context is released (and re-created on the next use)."""
+        c, self._ctx = self._ctx, None
+        if c is not None:
+            c.close()
+
+    def __del__(self):
+        try:
+            self.Close()
+            if getattr(self, "_o", None):
+                _lib.load().kc_zstd_dopts_free(self._o)
+                self._o = None
+        except Exception:
+            pass
+
+
+def NewReader(r, *opts, **kw):
+    """zstd.NewReader(r, opts...) (decoder.go:88).  r must be None: the decoder serves DecodeAll and its batched forms; a stream
+    to read from is the streaming reader, which is not part of the device path."""
+    if r is not None:
+        raise NotImplementedError("zstd.NewReader over an io.Reader (Read / WriteTo) is not served by the device path: pass None and use DecodeAll")
+    return Decoder(*opts, **kw)

@@ -18,6 +18,7 @@
  *   kc_s2_max_encoded_len       == s2.MaxEncodedLen                      s2/encode.go:389-418
  *   kc_s2_encode_stream_dev     == s2.Writer.EncodeBuffer framing        s2/writer.go:357-451
  *   kc_zstd_decode_units_dev    == N x Decoder.DecodeAll (verifier)       zstd/framedec.go, blockdec.go, seqdec_generic.go
+ *   kc_zstd_decode_all[_dev]    == N x (*Decoder).DecodeAll(input, nil)   zstd/decoder.go:319-410 (the decoder as a product)
  *   kc_s2_decode_blocks_dev     == N x s2.Decode (verifier)              s2/decode.go:58, decode_other.go:22
  *   kc_xxh64_units_dev          == xxhash.Digest over each unit          zstd/internal/xxhash/xxhash.go:27-230
  */
@@ -349,6 +350,52 @@ kc_status kc_zstd_decode_units_dev(kc_ctx* ctx, const uint8_t* d_enc, const uint
  * WithEncoderDictRaw, or with WithEncoderDict as long as they do not reuse the dictionary's entropy tables */
 kc_status kc_zstd_decode_units_dict_dev(kc_ctx* ctx, const uint8_t* d_enc, const uint64_t* enc_off, uint32_t n_units, uint8_t* d_dst,
                                         const uint64_t* dst_off, uint32_t* status, const uint8_t* dict, uint64_t dict_len);
+/* ---- zstd.Decoder.DecodeAll over N independent inputs (zstd/decoder.go:319-410) ----
+ * The decoder as a product: no decoded length is supplied; an input is any concatenation of frames and skippable frames, as DecodeAll
+ * takes it; window, size and dictionary rules are the reference's; untrusted input is safe (every read is checked against the
+ * input's end, every write against the input's own output range; a failing input never touches another input's bytes).
+ *
+ * Options == decoderOptions (zstd/decoder_options.go): kc_zstd_dopts_default returns a new object with the reference's defaults
+ * (WithDecoderMaxMemory 64 GiB, WithDecoderMaxWindow 512 MiB); the setters return 0, or -1 where the reference's option returns an
+ * error.  kc_zstd_dopts_dict == WithDecoderDicts (one full-format dictionary per call: ID, content, repeat offsets and the Huffman /
+ * FSE tables a frame's first block may reuse; parsed once, here), kc_zstd_dopts_dict_raw == WithDecoderDictRaw; any number may be
+ * registered, a frame's Dictionary_ID picks one, a later registration of an ID replaces an earlier one.  The bytes are copied.
+ * One deviation: a single frame of more than 4 GiB - 256 decoded bytes is refused with KC_ZD_SIZE_EXCEEDED whatever the limit. */
+typedef struct kc_zstd_dopts kc_zstd_dopts;
+kc_zstd_dopts* kc_zstd_dopts_default(void);
+void kc_zstd_dopts_free(kc_zstd_dopts* o);
+int kc_zstd_dopts_max_memory(kc_zstd_dopts* o, uint64_t n);
+int kc_zstd_dopts_max_window(kc_zstd_dopts* o, uint64_t n);
+int kc_zstd_dopts_ignore_checksum(kc_zstd_dopts* o, int b);
+int kc_zstd_dopts_dict(kc_zstd_dopts* o, const uint8_t* blob, uint64_t len);
+int kc_zstd_dopts_dict_raw(kc_zstd_dopts* o, uint32_t id, const uint8_t* content, uint64_t len);
+/* Per-input status: 0, or the class of the reference's error */
+enum {
+    KC_ZD_OK = 0,
+    KC_ZD_MAGIC = 1,            /* ErrMagicMismatch */
+    KC_ZD_EOF = 2,              /* the input ends inside a frame (io.ErrUnexpectedEOF) */
+    KC_ZD_UNKNOWN_DICT = 3,     /* ErrUnknownDictionary */
+    KC_ZD_WINDOW_EXCEEDED = 4,  /* ErrWindowSizeExceeded */
+    KC_ZD_SIZE_EXCEEDED = 5,    /* ErrDecoderSizeExceeded */
+    KC_ZD_CRC = 6,              /* ErrCRCMismatch */
+    KC_ZD_CORRUPT = 7           /* every other error */
+};
+/* src: the inputs, concatenated; in_off: n + 1 ascending offsets into it.  Input i decodes to dst + out_off[i] .. out_off[i + 1]
+ * (dense: out_off[0] == 0); an input that fails gets status[i] != 0 and an empty range, its neighbours are not affected.  in_off,
+ * out_off, status (and bound) are HOST arrays in both forms; src / dst are device memory for _dev, host memory otherwise.
+ * KC_ERR_DST_TOO_SMALL when the decoded inputs do not fit dst_cap: nothing is written past dst_cap, out_off and status are
+ * unspecified.  The device memory a call takes stays inside the context's scratch ceiling (KC_OPT_MAX_SCRATCH_MIB, and what is free):
+ * a batch whose staging does not fit is cut, an input that cannot fit alone gets KC_ZD_SIZE_EXCEEDED.
+ * kc_zstd_decode_all_bound[_dev]: the plan alone — bound[i] = the decoded size of input i, exact when every frame carries its
+ * content size, else an upper bound from the block headers (at most the size limit); status[i] = the first header-level error. */
+kc_status kc_zstd_decode_all_dev(kc_ctx* ctx, const kc_zstd_dopts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n,
+                                 uint8_t* d_dst, uint64_t dst_cap, uint64_t* out_off, uint32_t* status);
+kc_status kc_zstd_decode_all(kc_ctx* ctx, const kc_zstd_dopts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst,
+                             uint64_t dst_cap, uint64_t* out_off, uint32_t* status);
+kc_status kc_zstd_decode_all_bound_dev(kc_ctx* ctx, const kc_zstd_dopts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n,
+                                       uint64_t* bound, uint32_t* status);
+kc_status kc_zstd_decode_all_bound(kc_ctx* ctx, const kc_zstd_dopts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n,
+                                   uint64_t* bound, uint32_t* status);
 /* Single-block form with the WriterCustomEncoder contract (s2/writer.go:1053-1064): no varint header;
  * returns bytes used, 0 = incompressible (store raw), <0 = fall back to the built-in encoder.
  * "The function should expect to be called concurrently" (writer.go:1058; s2.Writer calls it from one goroutine per block,

@@ -6,7 +6,9 @@
 # device (streams are synchronous here) and is not part of the CPU or GPU suites.  Tests too large for the emulator time out
 # (--timeout) and show as crashed workers.  The device DECODERS (kc_zstd_decode.hip, kc_s2_decode.hip) are verifiers written for the
 # hardware's lockstep waves (a wavefront fence between one lane's table build and the other lanes' reads, no rendezvous the emulator
-# could see): their tests fail here by construction — deselect them (-k "not decode").
+# could see): their tests fail here by construction — deselect them (-k "not decode").  The DecodeAll product path
+# (kc_zstd_decode_all.hip) synchronises with KC_WAVE_SYNC and does run here: tools/emu_host_check.sh tests/test_gpu_zstd_decode_all.py
+# is the rehearsal its corrupt-input tests want before they go to a GPU.
 #   tools/emu_host_check.sh [pytest args...]      e.g.  tools/emu_host_check.sh tests/test_gpu_s2.py -k "not full_size and not decode"
 #   HIPEMU_POISON=rand|<byte>   NOASAN=1   JOBS=7   TIMEOUT=600   SKIP_BUILD=1 (a second run beside a running one)
 cd "$(dirname "$0")/.."

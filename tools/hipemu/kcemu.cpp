@@ -14,8 +14,83 @@
 #include <vector>
 #include "../../compress_amd/csrc/kc_s2_best.hip"
 #include "../../compress_amd/csrc/kc_zstd_match_best.hip"
+#include "../../compress_amd/csrc/kc_zstd_plan.hip"
+#include "../../compress_amd/csrc/kc_zstd_decode_all.hip"
+#include "../../compress_amd/csrc/kc_dict.cpp"       // (host code: the dictionary loader the decoder options use)
+#include "../../compress_amd/csrc/kc_zdec_host.h"
 
 extern "C" {
+
+// zstd.Decoder.DecodeAll over n inputs on the emulator: the plan kernel (both passes), the decode kernel, XXH64 of the decoded frames,
+// the host's verdict per input (kc_zdec_host.h) and the compaction into dst — kc_zstd_dec_api.cpp's sequence as one batch in plain
+// memory.  dict_blobs: n_dicts full-format dictionaries back to back (dict_off: n_dicts + 1 offsets), all registered at once.
+// Returns 0, -2 when dst_cap is too small, -1 on a dictionary the loader refuses.
+int kcemu_zstd_decode_all(const uint8_t* src, const uint64_t* in_off, uint32_t n, uint64_t max_memory, uint64_t max_window, int ignore_checksum,
+                          const uint8_t* dict_blobs, const uint64_t* dict_off, uint32_t n_dicts, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off,
+                          uint32_t* status) {
+    std::vector<KcZdDict> dicts(n_dicts);
+    std::vector<uint8_t> arena(16);
+    for (uint32_t k = 0; k < n_dicts; k++) {
+        const uint8_t* content = nullptr;
+        uint64_t clen = 0;
+        if (kc_dict_load_decoder(dict_blobs + dict_off[k], dict_off[k + 1] - dict_off[k], &dicts[k], &content, &clen) != 0) return -1;
+        dicts[k].content_off = arena.size();
+        arena.insert(arena.end(), content, content + clen);
+        arena.resize((arena.size() + 15) & ~(size_t)15);
+    }
+    std::vector<uint32_t> nf(n + 1, 0), exact(n + 1, 0), st(n + 1, 0), frame0(n + 1, 0);
+    std::vector<uint64_t> bound(n + 1, 0), slotb(n + 1, 0), slot0(n + 1, 0);
+    KcZdPlanParams P;
+    memset(&P, 0, sizeof(P));
+    P.src = src; P.in_off = in_off; P.n = n; P.max_memory = max_memory; P.max_window = max_window;
+    P.dicts = n_dicts ? dicts.data() : nullptr; P.n_dicts = n_dicts;
+    P.n_frames = nf.data(); P.bound = bound.data(); P.slot_bytes = slotb.data(); P.exact = exact.data(); P.status = st.data();
+    kc_launch_zstd_plan(P, nullptr);
+    uint32_t nfr = 0;
+    uint64_t slots = 0;
+    for (uint32_t i = 0; i < n; i++) { frame0[i] = nfr; slot0[i] = slots; nfr += nf[i]; slots += slotb[i]; }
+    std::vector<KcZdFrame> fr(nfr + 1);
+    std::vector<uint8_t> stage(slots + 64, 0xA7), lits((size_t)(nfr + 1) * KC_ZD_LIT_STRIDE, 0xA7);
+    std::vector<uint32_t> fsize(nfr + 1, 0), fstatus(nfr + 1, 0), fcrc(nfr + 1, 0), csize(nfr + 1, 0);
+    std::vector<uint64_t> hoff(2 * (size_t)nfr + 2, 0), hash(2 * (size_t)nfr + 2, 0), soff(nfr + 1, 0), ooff(nfr + 1, 0);
+    if (nfr) {
+        P.frame0 = frame0.data(); P.slot0 = slot0.data(); P.frames = fr.data();
+        kc_launch_zstd_plan(P, nullptr);
+        KcZdDecodeParams D;
+        memset(&D, 0, sizeof(D));
+        D.src = src; D.frames = fr.data(); D.n_frames = nfr; D.stage = stage.data(); D.lits = lits.data(); D.dicts = dicts.data();
+        D.dict_arena = arena.data(); D.max_memory = max_memory; D.out_size = fsize.data(); D.status = fstatus.data(); D.crc_stored = fcrc.data();
+        D.hash_off = hoff.data();
+        kc_launch_zstd_decode_all(D, nullptr);
+        if (!ignore_checksum) {
+            hipemu::set_group(4);
+            kc_launch_xxh64(stage.data(), hoff.data(), 2 * nfr - 1, hash.data(), nullptr);
+            hipemu::set_group(64);
+        }
+    }
+    uint64_t pos = 0;
+    out_off[0] = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        uint64_t total = 0;
+        if (st[i] == 0 && nf[i]) {
+            const uint32_t f0 = frame0[i];
+            st[i] = kc_zd_settle_input(fr.data() + f0, fstatus.data() + f0, fsize.data() + f0, fcrc.data() + f0, hash.data() + 2 * (size_t)f0, nf[i],
+                                       max_memory, ignore_checksum != 0, &total);
+            if (st[i]) total = 0;
+        }
+        if (pos + total > dst_cap) return -2;
+        for (uint32_t f = frame0[i]; f < frame0[i] + nf[i]; f++) {
+            soff[f] = fr[f].slot_off;
+            ooff[f] = pos;
+            csize[f] = st[i] ? 0u : fsize[f];
+            pos += csize[f];
+        }
+        status[i] = st[i];
+        out_off[i + 1] = pos;
+    }
+    kc_launch_compact(stage.data(), soff.data(), csize.data(), ooff.data(), dst, nfr, nullptr);
+    return 0;
+}
 
 // kc_zstd_prime_kernel: n table slots (zeroed by the caller) primed from the first unit_hist[u] bytes of their units; reverse = the
 // emulator keeps the LOWEST lane's value where lanes of one store instruction share an address (the hardware may keep any)

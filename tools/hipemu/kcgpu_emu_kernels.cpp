@@ -16,3 +16,5 @@
 #include "../../compress_amd/csrc/kc_zstd_match_best.hip"
 #include "../../compress_amd/csrc/kc_zstd_decode.hip"
 #include "../../compress_amd/csrc/kc_s2_decode.hip"
+#include "../../compress_amd/csrc/kc_zstd_plan.hip"
+#include "../../compress_amd/csrc/kc_zstd_decode_all.hip"

@@ -10,6 +10,8 @@ KC_OK = 0
 # per-input status classes of zstd.Decoder.DecodeAll (include/kcgpu.h KC_ZD_*)
 ZD_NAMES = {0: "KC_ZD_OK", 1: "KC_ZD_MAGIC", 2: "KC_ZD_EOF", 3: "KC_ZD_UNKNOWN_DICT", 4: "KC_ZD_WINDOW_EXCEEDED", 5: "KC_ZD_SIZE_EXCEEDED",
             6: "KC_ZD_CRC", 7: "KC_ZD_CORRUPT"}
+# per-input status classes of s2.Reader / s2.Decode (include/kcgpu.h KC_S2D_*)
+S2D_NAMES = {0: "KC_S2D_OK", 1: "KC_S2D_CORRUPT", 2: "KC_S2D_CRC", 3: "KC_S2D_UNSUPPORTED", 4: "KC_S2D_SIZE_EXCEEDED"}
 KC_ERR_BAD_ARG, KC_ERR_DST_TOO_SMALL, KC_ERR_HIP, KC_ERR_UNSUPPORTED, KC_ERR_NO_DEVICE, KC_ERR_INTERNAL = -1, -2, -3, -4, -5, -6
 _NAMES = {0: "KC_OK", -1: "KC_ERR_BAD_ARG", -2: "KC_ERR_DST_TOO_SMALL", -3: "KC_ERR_HIP", -4: "KC_ERR_UNSUPPORTED",
           -5: "KC_ERR_NO_DEVICE", -6: "KC_ERR_INTERNAL"}
@@ -47,6 +49,9 @@ SYMBOLS = [
     "kc_last_timings", "kc_corpus_fill", "kc_ctx_set_option", "kc_ctx_get_option", "kc_zstd_encode_jobs", "kc_zstd_job_size", "kc_zstd_overlap_size",
     "kc_zstd_dopts_default", "kc_zstd_dopts_free", "kc_zstd_dopts_max_memory", "kc_zstd_dopts_max_window", "kc_zstd_dopts_ignore_checksum", "kc_zstd_dopts_dict", "kc_zstd_dopts_dict_raw",
     "kc_zstd_decode_all_dev", "kc_zstd_decode_all", "kc_zstd_decode_all_bound_dev", "kc_zstd_decode_all_bound",
+    "kc_s2_ropts_default", "kc_s2_ropts_free", "kc_s2_ropts_max_block_size", "kc_s2_ropts_ignore_crc", "kc_s2_ropts_ignore_stream_identifier",
+    "kc_s2_decode_streams_dev", "kc_s2_decode_streams", "kc_s2_decode_streams_bound_dev", "kc_s2_decode_streams_bound",
+    "kc_s2_decode_blocks_all_dev", "kc_s2_decode_blocks_all", "kc_s2_decode_blocks_all_bound_dev", "kc_s2_decode_blocks_all_bound",
     "kc_probe_table_pattern", "kc_probe_pcie", "kc_ctx_trim", "kc_device_trim", "kc_s2_hook_declined", "kc_create_error", "kc_host_alloc", "kc_host_free",
 ]
 
@@ -181,6 +186,32 @@ def load():
         f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp]
         f.restype = C.c_int
     L.kc_s2_decode_blocks_dev.restype = C.c_int
+    L.kc_s2_ropts_default.argtypes = []
+    L.kc_s2_ropts_default.restype = vp
+    L.kc_s2_ropts_free.argtypes = [vp]
+    L.kc_s2_ropts_free.restype = None
+    L.kc_s2_ropts_max_block_size.argtypes = [vp, C.c_int64]
+    L.kc_s2_ropts_max_block_size.restype = C.c_int
+    for n in ("ignore_crc", "ignore_stream_identifier"):
+        f = getattr(L, "kc_s2_ropts_" + n)
+        f.argtypes = [vp, C.c_int]
+        f.restype = C.c_int
+    for n in ("kc_s2_decode_streams_dev", "kc_s2_decode_streams"):
+        f = getattr(L, n)
+        f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, u64, vp, vp]
+        f.restype = C.c_int
+    for n in ("kc_s2_decode_streams_bound_dev", "kc_s2_decode_streams_bound"):
+        f = getattr(L, n)
+        f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp]
+        f.restype = C.c_int
+    for n in ("kc_s2_decode_blocks_all_dev", "kc_s2_decode_blocks_all"):
+        f = getattr(L, n)
+        f.argtypes = [vp, vp, vp, C.c_uint32, vp, u64, vp, vp]
+        f.restype = C.c_int
+    for n in ("kc_s2_decode_blocks_all_bound_dev", "kc_s2_decode_blocks_all_bound"):
+        f = getattr(L, n)
+        f.argtypes = [vp, vp, vp, C.c_uint32, vp, vp]
+        f.restype = C.c_int
     L.kc_s2_encode_block.argtypes = [vp, vp, u64, vp, u64]
     L.kc_s2_encode_block.restype = C.c_int64
     L.kc_s2_hook_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]

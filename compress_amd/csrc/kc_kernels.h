@@ -289,6 +289,48 @@ struct KcZdDecodeParams {
                                  // hashes every frame's decoded bytes at the even indices
 };
 void kc_launch_zstd_decode_all(const KcZdDecodeParams& P, hipStream_t st);
+// ---- s2.Reader / s2.Decode as a product (kc_s2_plan_dev.h, kc_s2_plan.hip, kc_s2_decode_all.hip; host side kc_s2_dec_api.cpp) ----
+// Per-stream / per-chunk status classes (include/kcgpu.h KC_S2D_*)
+enum { KCS2D_OK = 0, KCS2D_CORRUPT = 1, KCS2D_CRC = 2, KCS2D_UNSUPPORTED = 3, KCS2D_SIZE = 4 };
+#define KC_S2C_STORED 1u   // KcS2Chunk.kind: an uncompressed chunk (the body is the bytes), else a block (uvarint length + tags)
+#define KC_S2C_NOCRC 2u    // ... a bare block: nothing stored to compare with
+// One data chunk of one input, written by the plan kernel and consumed by the decode kernel.
+struct KcS2Chunk {
+    uint64_t body_off;           // position in src: behind the chunk's checksum (a bare block: its first byte)
+    uint64_t out_off;            // where it decodes to in dst
+    uint32_t body_len;
+    uint32_t dlen;               // decoded length, from the chunk's own header
+    uint32_t crc;                // the stored (masked) CRC32C
+    uint32_t kind;               // KC_S2C_*
+    uint32_t stream, index;      // the input it belongs to and its number among that input's data chunks
+};
+struct KcS2PlanParams {
+    const uint8_t* src;
+    const uint64_t* in_off;      // device, n + 1
+    uint32_t n;
+    uint32_t max_block;          // ReaderMaxBlockSize
+    uint32_t max_buf;            // MaxEncodedLen(max_block) + 4: the largest chunk the Reader buffers (s2/reader.go:42)
+    int32_t ignore_id;           // ReaderIgnoreStreamIdentifier
+    int32_t blocks;              // 1: the inputs are bare blocks (s2.Decode), not framed streams
+    // first pass (chunks == null): per input the data chunks in front of the first header-level error, their decoded bytes, that error
+    uint32_t* n_chunks;
+    uint64_t* bound;
+    uint32_t* status;
+    // second pass: the same walk writes the chunk records
+    const uint32_t* chunk0;      // device, per input: index of its first record
+    const uint64_t* out0;        // device, per input: where its range starts in dst
+    KcS2Chunk* chunks;
+};
+void kc_launch_s2_plan(const KcS2PlanParams& P, hipStream_t st);
+struct KcS2DecodeAllParams {
+    const uint8_t* src;
+    const KcS2Chunk* chunks;
+    uint32_t n_chunks;
+    uint8_t* dst;
+    int32_t ignore_crc;
+    uint32_t* status;            // per chunk: KCS2D_OK / KCS2D_CORRUPT / KCS2D_CRC
+};
+void kc_launch_s2_decode_all(const KcS2DecodeAllParams& P, hipStream_t st);
 // default: 2^14 entries; better: long 2^17 + short 2^14 (blocks > 64 KiB), long 2^16 + short 2^13 (all blocks <= 64 KiB)
 static inline size_t kc_s2_table_bytes(int level, uint64_t max_block_len, int variant = 0) {
     // the assembly forms of the better levels take 2^17 + 2^14 entries from 16 KiB on (Snappy-compatible: above 64 KiB; 2^16 + 2^13 below)

@@ -32,57 +32,6 @@ __device__ unsigned long long kc_s2_prof[16];
 #define S2L_POS_MASK 0xFFFFFFu
 #define S2L_TAIL 544  // bytes behind the block in LDS: the fused step loads up to 63 x 8 bytes past a position before it looks at the bounds
 
-// CRC32C of [0, len) read through rd32 / rdb, all 64 lanes cooperating: lane j takes bytes [j*C, (j+1)*C); the raw
-// (init 0) remainders are combined left to right, acc = advance(acc, C zero bytes) ^ part[j], with the 32 columns of
-// "advance by C zero bytes" computed by lanes 0..31.  The 0xFFFFFFFF initial value equals an XOR into the first word.
-template <class RD32, class RDB>
-__device__ __forceinline__ uint32_t s2_crc32c_wave(RD32 rd32, RDB rdb, int len, const uint32_t (*T)[256], uint32_t* colM, uint32_t* part, int lane) {
-    auto step4 = [&](uint32_t c) -> uint32_t { return T[3][c & 0xFF] ^ T[2][(c >> 8) & 0xFF] ^ T[1][(c >> 16) & 0xFF] ^ T[0][c >> 24]; };
-    if (len < 512) {  // short: every lane runs the plain loop (uniform)
-        uint32_t c = 0xFFFFFFFFu;
-        int i = 0;
-        for (; i + 4 <= len; i += 4) c = step4(c ^ rd32(i));
-        for (; i < len; i++) c = T[0][(c ^ rdb(i)) & 0xFF] ^ (c >> 8);
-        return c ^ 0xFFFFFFFFu;
-    }
-    const int C = ((len + 63) / 64 + 3) & ~3;
-    const int b = lane * C;
-    const int e = b + C < len ? b + C : len;
-    uint32_t c = 0;
-    if (b < len) {
-        int i = b;
-        for (; i + 4 <= e; i += 4) {
-            uint32_t w = rd32(i);
-            if (i == 0) w ^= 0xFFFFFFFFu;
-            c = step4(c ^ w);
-        }
-        for (; i < e; i++) c = T[0][(c ^ rdb(i)) & 0xFF] ^ (c >> 8);
-    }
-    if (lane < 32) {
-        uint32_t v = 1u << lane;
-        for (int i = 0; i < C; i += 4) v = step4(v);
-        colM[lane] = v;
-    }
-    part[lane] = c;
-    KC_WAVE_SYNC();
-    const int nfull = len / C;
-    uint32_t acc = 0;
-    for (int j = 0; j < nfull; j++) {
-        uint32_t a = 0;
-        for (int k = 0; k < 32; k++) if ((acc >> k) & 1u) a ^= colM[k];
-        acc = a ^ part[j];
-    }
-    const int r = len - nfull * C;
-    if (r > 0) {
-        int i = 0;
-        for (; i + 4 <= r; i += 4) acc = step4(acc);
-        for (; i < r; i++) acc = T[0][acc & 0xFF] ^ (acc >> 8);
-        acc ^= part[nfull];
-    }
-    KC_WAVE_SYNC();
-    return acc ^ 0xFFFFFFFFu;
-}
-
 // LEVEL 0: s2.Encode, 2: s2.EncodeSnappy; SRCLDS: block <= 64 KiB, held in LDS; ONESTEP (with SRCLDS): one probe step at a time,
 // every lane the same — with the block in LDS a step is two LDS round trips whether or not other steps run beside it, so the
 // speculative round's machinery (positions, markers, ballots, winner selection: ~600 instructions for one sequence) buys nothing

@@ -1,0 +1,80 @@
+// kc_s2_plan_dev.h — the chunk walk of s2.Reader (s2/reader.go:259-404) over one input, written once for the device (one lane per
+// input: kc_s2_plan.hip) and the host (the host-buffer entry points size their batches with it: kc_s2_dec_api.cpp).  It reads chunk
+// headers, stream identifiers and the uvarint in front of a compressed chunk's tags; it never touches a chunk's payload.  Every read
+// is checked against the input's end.
+#pragma once
+#include <stdint.h>
+#include "kc_kernels.h"
+
+#define KC_S2_MAX_CHUNK 0xFFFFFFu          // maxChunkSize (s2/s2.go:93)
+#define KC_S2_MAX_SNAPPY_BLOCK 65536u      // maxSnappyBlockSize (s2/s2.go:99)
+
+// decodedLen (s2/decode.go:36-47) of the block in [pos, end): a uvarint of at most 5 bytes whose value fits 32 bits
+__host__ __device__ inline bool kc_s2_decoded_len(const uint8_t* in, uint64_t pos, uint64_t end, uint32_t* dlen, uint32_t* hdr) {
+    uint64_t v = 0;
+    for (uint32_t i = 0; i < 5; i++) {
+        if (pos + i >= end) return false;  // binary.Uvarint: buffer too small
+        const uint32_t b = in[pos + i];
+        v |= (uint64_t)(b & 0x7fu) << (7 * i);
+        if (b < 0x80u) {
+            if (v > 0xffffffffull) return false;
+            *dlen = (uint32_t)v;
+            *hdr = i + 1;
+            return true;
+        }
+    }
+    return false;  // more than 5 bytes
+}
+
+struct KcS2Walk {
+    uint32_t status;    // the first header-level error (KCS2D_*), 0: the walk reached the input's end at a chunk boundary
+    uint32_t n_chunks;  // data chunks in front of it
+    uint64_t total;     // their decoded bytes
+};
+
+// emit(index, body_off, body_len, kind, out_rel, dlen, crc) is called for every data chunk in stream order.
+template <class Emit>
+__host__ __device__ inline KcS2Walk kc_s2_walk(const uint8_t* in, uint64_t pos, const uint64_t end, uint32_t max_block, uint32_t max_buf, bool ignore_id,
+                                               Emit emit) {
+    KcS2Walk W;
+    W.status = KCS2D_OK; W.n_chunks = 0; W.total = 0;
+    bool readHeader = ignore_id, snappy = false;
+    while (pos < end) {  // (nothing left: io.EOF from the 4-byte read, the clean end)
+        if (end - pos < 4) { W.status = KCS2D_CORRUPT; break; }
+        const uint32_t type = in[pos];
+        const uint32_t chunkLen = (uint32_t)in[pos + 1] | ((uint32_t)in[pos + 2] << 8) | ((uint32_t)in[pos + 3] << 16);
+        pos += 4;
+        if (!readHeader) {  // before the type switch: a leading padding chunk is corrupt too (reader.go:263-269)
+            if (type != 0xffu) { W.status = KCS2D_CORRUPT; break; }
+            readHeader = true;
+        }
+        if (type <= 0x01u) {
+            if (chunkLen < 4 || chunkLen > max_buf) { W.status = KCS2D_CORRUPT; break; }
+            if (end - pos < chunkLen) { W.status = KCS2D_CORRUPT; break; }
+            const uint32_t crc = (uint32_t)in[pos] | ((uint32_t)in[pos + 1] << 8) | ((uint32_t)in[pos + 2] << 16) | ((uint32_t)in[pos + 3] << 24);
+            uint32_t dl = chunkLen - 4, hdr = 0;
+            if (type == 0x00u && !kc_s2_decoded_len(in, pos + 4, pos + chunkLen, &dl, &hdr)) { W.status = KCS2D_CORRUPT; break; }
+            if (snappy && dl > KC_S2_MAX_SNAPPY_BLOCK) { W.status = KCS2D_CORRUPT; break; }
+            if (dl > max_block) { W.status = KCS2D_CORRUPT; break; }
+            emit(W.n_chunks, pos + 4, chunkLen - 4, type == 0x01u ? KC_S2C_STORED : 0u, W.total, dl, crc);
+            W.n_chunks++;
+            W.total += dl;
+            pos += chunkLen;
+            continue;
+        }
+        if (type == 0xffu) {  // stream identifier: S2 or Snappy, also in the middle of an input (concatenated streams)
+            if (chunkLen != 6 || end - pos < 6) { W.status = KCS2D_CORRUPT; break; }
+            const uint8_t* m = in + pos;
+            if (m[0] == 'S' && m[1] == '2' && m[2] == 's' && m[3] == 'T' && m[4] == 'w' && m[5] == 'O') snappy = false;
+            else if (m[0] == 's' && m[1] == 'N' && m[2] == 'a' && m[3] == 'P' && m[4] == 'p' && m[5] == 'Y') snappy = true;
+            else { W.status = KCS2D_CORRUPT; break; }
+            pos += 6;
+            continue;
+        }
+        if (type <= 0x7fu) { W.status = KCS2D_UNSUPPORTED; break; }  // reserved unskippable chunks
+        if (chunkLen > KC_S2_MAX_CHUNK) { W.status = KCS2D_UNSUPPORTED; break; }
+        if (end - pos < chunkLen) { W.status = KCS2D_CORRUPT; break; }  // padding, index and other skippable chunks
+        pos += chunkLen;
+    }
+    return W;
+}

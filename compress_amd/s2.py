@@ -1,4 +1,5 @@
-"""Host mirror of the reference's S2 block API (s2/encode.go) over include/kcgpu.h."""
+"""Host mirror of the reference's S2 API over include/kcgpu.h: the block encoders (s2/encode.go), s2.Writer (s2/writer.go) and, for
+reading, s2.Decode / s2.DecodedLen (s2/decode.go) and s2.Reader's DecodeConcurrent with its batched forms (s2/reader.go)."""
 import ctypes as C
 import threading
 
@@ -168,10 +169,10 @@ def WriterFlushOnWrite():
     return lambda w: setattr(w, "flushOnWrite", True)
 
 
-def _unsupported(name):
+def _unsupported(name, what="writer"):
     def opt(*a, **k):
         def apply(w):
-            raise NotImplementedError("s2.%s is not served by the device path; use the reference writer" % name)
+            raise NotImplementedError("s2.%s is not served by the device path; use the reference %s" % (name, what))
         return apply
     return opt
 
@@ -506,3 +507,216 @@ class Writer:
 
 def NewWriter(w, *opts, **kw):
     return Writer(w, *opts, **kw)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# s2.Reader / s2.Decode (s2/reader.go, s2/decode.go) over the device path: whole inputs, in batches.  Every input is decoded
+# as io.ReadAll(s2.NewReader(input)) would; the sequential interface (Read, Skip, ReadSeeker, ReadByte) and skippable-chunk
+# callbacks stay with the reference.
+# ---------------------------------------------------------------------------------------------------------------------
+class S2DecodeError(ValueError):
+    """The reader refused an input.  `name` is the class of the reference's error: KC_S2D_CORRUPT (ErrCorrupt), KC_S2D_CRC (ErrCRC),
+    KC_S2D_UNSUPPORTED (ErrUnsupported), or KC_S2D_SIZE_EXCEEDED (an input too large for the scratch ceiling of a host-buffer call)."""
+
+    def __init__(self, status):
+        self.status = int(status)
+        self.name = _lib.S2D_NAMES.get(self.status, str(self.status))
+        super().__init__("s2: %s" % self.name)
+
+
+def DecodedLen(src):
+    """s2.DecodedLen (s2/decode.go:29-47), on the host: the uvarint in front of a block, at most 5 bytes and 32 bits."""
+    src = bytes(src[:6])
+    v = 0
+    for i, b in enumerate(src[:5]):
+        v |= (b & 0x7F) << (7 * i)
+        if b < 0x80:
+            if v > 0xFFFFFFFF:
+                break
+            return v
+    raise S2DecodeError(1)
+
+
+def _ropt(name, *args):
+    def apply(r):
+        if getattr(_lib.load(), "kc_s2_ropts_" + name)(r._o, *args) != 0:
+            raise ValueError("s2 reader option %s rejected" % name)
+    return apply
+
+
+def ReaderMaxBlockSize(n):
+    """s2.ReaderMaxBlockSize (reader.go:64): larger blocks are refused as corrupt.  Default and maximum 4 MiB."""
+    if n > _MAX_BLOCK or n <= 0:
+        raise ValueError("s2: block size too large. Must be <= 4MB and > 0")
+    return _ropt("max_block_size", int(n))
+
+
+def ReaderAllocBlock(n):
+    """s2.ReaderAllocBlock (reader.go:82): validated like the reference's; the device path has no buffer of that kind to size."""
+    if n > _MAX_BLOCK or n < 1024:
+        raise ValueError("s2: invalid ReaderAllocBlock. Must be <= 4MB and >= 1024")
+    return lambda r: None
+
+
+def ReaderIgnoreCRC():
+    """s2.ReaderIgnoreCRC (reader.go:120)."""
+    return _ropt("ignore_crc", 1)
+
+
+def ReaderIgnoreStreamIdentifier():
+    """s2.ReaderIgnoreStreamIdentifier (reader.go:95)."""
+    return _ropt("ignore_stream_identifier", 1)
+
+
+ReaderSkippableCB = _unsupported("ReaderSkippableCB", "reader")
+
+
+class Reader:
+    """s2.Reader for whole inputs: DecodeConcurrent, and its batched forms DecodeStreams (host buffers) / DecodeStreamsDevice
+    (device-resident) and DecodeBlocks / DecodeBlocksDevice for bare blocks.  An input is what s2.NewReader reads: any concatenation
+    of .s2 or Snappy-framed streams.  A failed input keeps its planned range in the output, zero-filled (include/kcgpu.h)."""
+
+    def __init__(self, r, *opts, device=0, stream=None):
+        L = _lib.load()
+        self._o = C.c_void_p(L.kc_s2_ropts_default())
+        if not self._o:
+            raise MemoryError("kc_s2_ropts_default")
+        for op in opts:
+            op(self)
+        self._device, self._stream = device, stream
+        self._ctx = None
+        self._r = r
+
+    def ctx(self):
+        if self._ctx is None:
+            self._ctx = _lib.Context(self._device, self._stream)
+        return self._ctx
+
+    def Reset(self, r):
+        """Reader.Reset (reader.go:177): read from r from now on; the options stay."""
+        self._r = r
+
+    def DecodeConcurrent(self, w, concurrent=0):
+        """Reader.DecodeConcurrent (reader.go:413): decode the whole of r to w, as one call.  Returns the bytes written; raises
+        S2DecodeError with the class of the reference's error (nothing is written then)."""
+        import numpy as np
+        data = self._r.read() if hasattr(self._r, "read") else bytes(self._r)
+        out = self.DecodeStreams(np.frombuffer(data, dtype=np.uint8), np.array([0, len(data)], dtype=np.uint64))[0]
+        if isinstance(out, S2DecodeError):
+            raise out
+        w.write(out)
+        return len(out)
+
+    def _host(self, fn_bound, fn, with_opts, src, in_off):
+        import numpy as np
+        ctx = self.ctx()
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = len(in_off) - 1
+        if len(src) == 0:
+            src = np.zeros(1, dtype=np.uint8)
+        o = (self._o,) if with_opts else ()
+        bound = np.zeros(max(n, 1), dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        ctx.check(getattr(ctx.L, fn_bound)(ctx.h, *o, src.ctypes.data, in_off.ctypes.data, n, bound.ctypes.data, status.ctypes.data))
+        if fn is None:
+            return bound[:n], status[:n]
+        cap = int(bound[:n].sum())
+        dst = np.empty(cap + 64, dtype=np.uint8)
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        ctx.check(getattr(ctx.L, fn)(ctx.h, *o, src.ctypes.data, in_off.ctypes.data, n, dst.ctypes.data, cap, out_off.ctypes.data, status.ctypes.data))
+        return [S2DecodeError(status[i]) if status[i] else dst[int(out_off[i]):int(out_off[i + 1])].tobytes() for i in range(n)]
+
+    def _dev(self, fn, with_opts, d_src_ptr, in_off, d_dst_ptr=None, dst_cap=0):
+        import numpy as np
+        ctx = self.ctx()
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = len(in_off) - 1
+        o = (self._o,) if with_opts else ()
+        first = np.zeros(n + 1, dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.uint32)
+        if d_dst_ptr is None:
+            ctx.check(getattr(ctx.L, fn)(ctx.h, *o, d_src_ptr, in_off.ctypes.data, n, first.ctypes.data, status.ctypes.data))
+            return first[:n], status[:n]
+        ctx.check(getattr(ctx.L, fn)(ctx.h, *o, d_src_ptr, in_off.ctypes.data, n, d_dst_ptr, int(dst_cap), first.ctypes.data, status.ctypes.data))
+        return first, status[:n]
+
+    def DecodeBounds(self, src, in_off, blocks=False):
+        """The plan alone (kc_s2_decode_streams_bound): per input the bytes it decodes to — from the chunk headers, exact if the input
+        stands — and the first header-level error.  blocks=True: the inputs are bare blocks (N x s2.DecodedLen).  Returns (uint64[n],
+        uint32[n])."""
+        if blocks:
+            return self._host("kc_s2_decode_blocks_all_bound", None, False, src, in_off)
+        return self._host("kc_s2_decode_streams_bound", None, True, src, in_off)
+
+    def DecodeStreams(self, src, in_off):
+        """N x io.ReadAll(s2.NewReader(input_i)) in one batch.  src: numpy uint8 (host), in_off: uint64[n+1].  Returns a list with, per
+        input, its bytes or the S2DecodeError that refused it."""
+        return self._host("kc_s2_decode_streams_bound", "kc_s2_decode_streams", True, src, in_off)
+
+    def DecodeBlocks(self, src, in_off):
+        """N x s2.Decode(nil, block_i) in one batch (bare blocks, S2 or Snappy): a list of bytes or S2DecodeError."""
+        return self._host("kc_s2_decode_blocks_all_bound", "kc_s2_decode_blocks_all", False, src, in_off)
+
+    def DecodeBoundsDevice(self, d_src_ptr, in_off, blocks=False):
+        """DecodeBounds over device-resident inputs (kc_s2_decode_streams_bound_dev): their sum is what d_dst must hold."""
+        if blocks:
+            return self._dev("kc_s2_decode_blocks_all_bound_dev", False, d_src_ptr, in_off)
+        return self._dev("kc_s2_decode_streams_bound_dev", True, d_src_ptr, in_off)
+
+    def DecodeStreamsDevice(self, d_src_ptr, in_off, d_dst_ptr, dst_cap):
+        """Device-resident form (pointers are ints): returns (uint64[n+1] planned offsets, uint32[n] status), host numpy.  A failed
+        input's range is zero-filled.  Raises KcError KC_ERR_DST_TOO_SMALL when the layout does not fit dst_cap (nothing is written)."""
+        return self._dev("kc_s2_decode_streams_dev", True, d_src_ptr, in_off, d_dst_ptr, dst_cap)
+
+    def DecodeBlocksDevice(self, d_src_ptr, in_off, d_dst_ptr, dst_cap):
+        """DecodeBlocks over device-resident blocks (kc_s2_decode_blocks_all_dev): (uint64[n+1] offsets, uint32[n] status)."""
+        return self._dev("kc_s2_decode_blocks_all_dev", False, d_src_ptr, in_off, d_dst_ptr, dst_cap)
+
+    def Read(self, p):
+        _unsupported("Reader.Read", "reader")()(self)
+
+    def Skip(self, n):
+        _unsupported("Reader.Skip", "reader")()(self)
+
+    def ReadSeeker(self, random=False, index=None):
+        _unsupported("Reader.ReadSeeker", "reader")()(self)
+
+    def ReadByte(self):
+        _unsupported("Reader.ReadByte", "reader")()(self)
+
+    def Close(self):
+        """The device context is released (and re-created on the next use)."""
+        c, self._ctx = self._ctx, None
+        if c is not None:
+            c.close()
+
+    def __del__(self):
+        try:
+            self.Close()
+            if getattr(self, "_o", None):
+                _lib.load().kc_s2_ropts_free(self._o)
+                self._o = None
+        except Exception:
+            pass
+
+
+def NewReader(r, *opts, **kw):
+    """s2.NewReader(r, opts...) (reader.go:31)."""
+    return Reader(r, *opts, **kw)
+
+
+_decoders = {}
+
+
+def Decode(dst, src, device=0):
+    """s2.Decode(dst, src) (s2/decode.go:58): the decoded block (dst is not reused).  Raises S2DecodeError (KC_S2D_CORRUPT)."""
+    import numpy as np
+    rd = _decoders.get(device)
+    if rd is None:
+        rd = _decoders[device] = Reader(None, device=device)
+    src = bytes(src)
+    out = rd.DecodeBlocks(np.frombuffer(src, dtype=np.uint8), np.array([0, len(src)], dtype=np.uint64))[0]
+    if isinstance(out, S2DecodeError):
+        raise out
+    return out

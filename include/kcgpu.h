@@ -396,6 +396,66 @@ kc_status kc_zstd_decode_all_bound_dev(kc_ctx* ctx, const kc_zstd_dopts* o, cons
                                        uint64_t* bound, uint32_t* status);
 kc_status kc_zstd_decode_all_bound(kc_ctx* ctx, const kc_zstd_dopts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n,
                                    uint64_t* bound, uint32_t* status);
+/* ---- s2.Reader / s2.Decode over N independent inputs (s2/reader.go:249-405, s2/decode.go:58-76) ----
+ * The S2 decoder as a product: no decoded length is supplied, CRCs are checked, errors carry the reference's classes; untrusted input
+ * is safe (every read is checked against the chunk's end, every write against the chunk's own output range).
+ * kc_s2_decode_blocks_dev above stays what it is: a verifier that is told every size and has status numbers of its own.
+ *
+ * Options == the ReaderOptions: kc_s2_ropts_default returns a new object with the reference's defaults (blocks up to 4 MiB, CRCs
+ * checked, a stream identifier required); kc_s2_ropts_max_block_size == ReaderMaxBlockSize (s2/reader.go:64: -1 for n <= 0 or
+ * n > 4 MiB), kc_s2_ropts_ignore_crc == ReaderIgnoreCRC, kc_s2_ropts_ignore_stream_identifier == ReaderIgnoreStreamIdentifier. */
+typedef struct kc_s2_ropts kc_s2_ropts;
+kc_s2_ropts* kc_s2_ropts_default(void);
+void kc_s2_ropts_free(kc_s2_ropts* o);
+int kc_s2_ropts_max_block_size(kc_s2_ropts* o, int64_t n);
+int kc_s2_ropts_ignore_crc(kc_s2_ropts* o, int b);
+int kc_s2_ropts_ignore_stream_identifier(kc_s2_ropts* o, int b);
+/* Per-input status: 0, or the class of the reference's error */
+enum {
+    KC_S2D_OK = 0,
+    KC_S2D_CORRUPT = 1,        /* ErrCorrupt */
+    KC_S2D_CRC = 2,            /* ErrCRC */
+    KC_S2D_UNSUPPORTED = 3,    /* ErrUnsupported */
+    KC_S2D_SIZE_EXCEEDED = 4   /* a limit of this library: host-buffer calls, an input that does not fit the scratch ceiling alone */
+};
+/* kc_s2_decode_streams[_dev] == io.ReadAll(s2.NewReader(input, options)) for every input (s2/reader.go:249-405).  src: the inputs,
+ * concatenated; in_off: n + 1 ascending offsets into it.  Input i is any concatenation of .s2 or Snappy-framed streams, as
+ * s2.NewReader reads it: stream identifiers of both kinds, compressed and uncompressed chunks, padding, index and other skippable
+ * chunks.  in_off, out_off, status (and bound) are HOST arrays in both forms; src / dst are device memory for _dev, host memory
+ * otherwise.
+ *
+ * The output contract differs from kc_zstd_decode_all's ON PURPOSE.  An S2 chunk states its decoded length in its header, so the sizes
+ * are exact before any byte is decoded: out_off (n + 1 entries, out_off[0] == 0, ascending) is the PLANNED layout — the prefix sum of
+ * bound — and every chunk decodes straight into dst at its planned place; there is no staging copy and no compaction pass.  An input
+ * that fails (status[i] != 0) KEEPS its planned range — the decoded bytes of the chunks in front of the first header-level error — and
+ * the library ZERO-FILLS that range before it returns: no byte decoded from a corrupt stream is left in dst, and its neighbours are
+ * untouched.  (The reference's sequential Reader hands out the chunks in front of an error; this API does not.)  The first failing
+ * chunk in stream order decides the status, in the reference's order inside a chunk: DecodedLen, Snappy's 64 KiB limit, the block
+ * size limit, the decode, the CRC.  KC_ERR_DST_TOO_SMALL when out_off[n] > dst_cap: nothing is written in that case.
+ *
+ * Host-buffer form: the inputs go to the device in groups cut between inputs, each group's bytes and decoded bytes within a quarter of
+ * the context's scratch ceiling (KC_OPT_MAX_SCRATCH_MIB, and what is free); an input that does not fit alone gets
+ * KC_S2D_SIZE_EXCEEDED and a zero-filled range.  It does not use the rolling host pipeline.
+ * kc_s2_decode_streams_bound[_dev]: the plan alone (s2/reader.go:259-404, the chunk headers) — bound[i] = the bytes input i decodes to,
+ * exact if the input stands; status[i] = the first header-level error.
+ * kc_s2_decode_blocks_all[_dev]: N bare blocks (uvarint length + body, S2 or Snappy) == N x s2.Decode(nil, block) (s2/decode.go:58-76)
+ * with the same output contract; every error is KC_S2D_CORRUPT.  _bound == N x s2.DecodedLen (s2/decode.go:29-47). */
+kc_status kc_s2_decode_streams_dev(kc_ctx* ctx, const kc_s2_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint8_t* d_dst,
+                                   uint64_t dst_cap, uint64_t* out_off, uint32_t* status);
+kc_status kc_s2_decode_streams(kc_ctx* ctx, const kc_s2_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst,
+                               uint64_t dst_cap, uint64_t* out_off, uint32_t* status);
+kc_status kc_s2_decode_streams_bound_dev(kc_ctx* ctx, const kc_s2_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n,
+                                         uint64_t* bound, uint32_t* status);
+kc_status kc_s2_decode_streams_bound(kc_ctx* ctx, const kc_s2_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n,
+                                     uint64_t* bound, uint32_t* status);
+kc_status kc_s2_decode_blocks_all_dev(kc_ctx* ctx, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint8_t* d_dst, uint64_t dst_cap,
+                                      uint64_t* out_off, uint32_t* status);
+kc_status kc_s2_decode_blocks_all(kc_ctx* ctx, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst, uint64_t dst_cap,
+                                  uint64_t* out_off, uint32_t* status);
+kc_status kc_s2_decode_blocks_all_bound_dev(kc_ctx* ctx, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint64_t* bound,
+                                            uint32_t* status);
+kc_status kc_s2_decode_blocks_all_bound(kc_ctx* ctx, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint64_t* bound,
+                                        uint32_t* status);
 /* Single-block form with the WriterCustomEncoder contract (s2/writer.go:1053-1064): no varint header;
  * returns bytes used, 0 = incompressible (store raw), <0 = fall back to the built-in encoder.
  * "The function should expect to be called concurrently" (writer.go:1058; s2.Writer calls it from one goroutine per block,

@@ -18,6 +18,42 @@
 #include "../../compress_amd/csrc/kc_zstd_decode_all.hip"
 #include "../../compress_amd/csrc/kc_dict.cpp"       // (host code: the dictionary loader the decoder options use)
 #include "../../compress_amd/csrc/kc_zdec_host.h"
+#include "../../compress_amd/csrc/kc_s2_plan.hip"
+#include "../../compress_amd/csrc/kc_s2_decode_all.hip"
+
+// s2.Reader / s2.Decode over n inputs on the emulator: the plan kernel (both passes), the decode kernel with its CRC, the verdict per
+// input (first failing chunk in stream order, else the plan's error) and the zero-fill of the failed ranges — kc_s2_dec_api.cpp's
+// sequence as one batch in plain memory.  Returns 0, -2 when dst_cap is too small (nothing written).
+static int kcemu_s2_decode(const KcS2PlanParams& P0, int ignore_crc, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* bound, uint32_t* status) {
+    KcS2PlanParams P = P0;
+    const uint32_t n = P.n;
+    std::vector<uint32_t> nc(n + 1, 0), st(n + 1, 0), chunk0(n + 1, 0);
+    std::vector<uint64_t> bd(n + 1, 0);
+    P.n_chunks = nc.data(); P.bound = bd.data(); P.status = st.data();
+    kc_launch_s2_plan(P, nullptr);
+    uint32_t total = 0;
+    out_off[0] = 0;
+    for (uint32_t i = 0; i < n; i++) { chunk0[i] = total; total += nc[i]; out_off[i + 1] = out_off[i] + bd[i]; bound[i] = bd[i]; }
+    if (out_off[n] > dst_cap) return -2;
+    std::vector<KcS2Chunk> ch(total + 1);
+    std::vector<uint32_t> cs(total + 1, 0xA7A7A7A7u);
+    if (total) {
+        P.chunk0 = chunk0.data(); P.out0 = out_off; P.chunks = ch.data();
+        kc_launch_s2_plan(P, nullptr);
+        KcS2DecodeAllParams D;
+        memset(&D, 0, sizeof(D));
+        D.src = P.src; D.chunks = ch.data(); D.n_chunks = total; D.dst = dst; D.ignore_crc = ignore_crc; D.status = cs.data();
+        kc_launch_s2_decode_all(D, nullptr);
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t v = 0;
+        for (uint32_t k = 0; k < nc[i] && !v; k++) v = cs[chunk0[i] + k];
+        if (!v) v = st[i];
+        status[i] = v;
+        if (v && bd[i]) memset(dst + out_off[i], 0, (size_t)bd[i]);
+    }
+    return 0;
+}
 
 extern "C" {
 
@@ -90,6 +126,22 @@ int kcemu_zstd_decode_all(const uint8_t* src, const uint64_t* in_off, uint32_t n
     }
     kc_launch_compact(stage.data(), soff.data(), csize.data(), ooff.data(), dst, nfr, nullptr);
     return 0;
+}
+
+int kcemu_s2_decode_streams(const uint8_t* src, const uint64_t* in_off, uint32_t n, uint32_t max_block, uint32_t max_buf, int ignore_crc, int ignore_id,
+                            uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* bound, uint32_t* status) {
+    KcS2PlanParams P;
+    memset(&P, 0, sizeof(P));
+    P.src = src; P.in_off = in_off; P.n = n; P.max_block = max_block; P.max_buf = max_buf; P.ignore_id = ignore_id;
+    return kcemu_s2_decode(P, ignore_crc, dst, dst_cap, out_off, bound, status);
+}
+
+int kcemu_s2_decode_blocks_all(const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* bound,
+                               uint32_t* status) {
+    KcS2PlanParams P;
+    memset(&P, 0, sizeof(P));
+    P.src = src; P.in_off = in_off; P.n = n; P.blocks = 1;
+    return kcemu_s2_decode(P, 1, dst, dst_cap, out_off, bound, status);
 }
 
 // kc_zstd_prime_kernel: n table slots (zeroed by the caller) primed from the first unit_hist[u] bytes of their units; reverse = the

@@ -11,7 +11,8 @@ KC_OK = 0
 ZD_NAMES = {0: "KC_ZD_OK", 1: "KC_ZD_MAGIC", 2: "KC_ZD_EOF", 3: "KC_ZD_UNKNOWN_DICT", 4: "KC_ZD_WINDOW_EXCEEDED", 5: "KC_ZD_SIZE_EXCEEDED",
             6: "KC_ZD_CRC", 7: "KC_ZD_CORRUPT"}
 # per-input status classes of s2.Reader / s2.Decode (include/kcgpu.h KC_S2D_*)
-S2D_NAMES = {0: "KC_S2D_OK", 1: "KC_S2D_CORRUPT", 2: "KC_S2D_CRC", 3: "KC_S2D_UNSUPPORTED", 4: "KC_S2D_SIZE_EXCEEDED"}
+S2D_NAMES = {0: "KC_S2D_OK", 1: "KC_S2D_CORRUPT", 2: "KC_S2D_CRC", 3: "KC_S2D_UNSUPPORTED", 4: "KC_S2D_SIZE_EXCEEDED", 5: "KC_S2D_EOF",
+             6: "KC_S2D_UNEXPECTED_EOF"}
 KC_ERR_BAD_ARG, KC_ERR_DST_TOO_SMALL, KC_ERR_HIP, KC_ERR_UNSUPPORTED, KC_ERR_NO_DEVICE, KC_ERR_INTERNAL = -1, -2, -3, -4, -5, -6
 _NAMES = {0: "KC_OK", -1: "KC_ERR_BAD_ARG", -2: "KC_ERR_DST_TOO_SMALL", -3: "KC_ERR_HIP", -4: "KC_ERR_UNSUPPORTED",
           -5: "KC_ERR_NO_DEVICE", -6: "KC_ERR_INTERNAL"}
@@ -52,6 +53,9 @@ SYMBOLS = [
     "kc_s2_ropts_default", "kc_s2_ropts_free", "kc_s2_ropts_max_block_size", "kc_s2_ropts_ignore_crc", "kc_s2_ropts_ignore_stream_identifier",
     "kc_s2_decode_streams_dev", "kc_s2_decode_streams", "kc_s2_decode_streams_bound_dev", "kc_s2_decode_streams_bound",
     "kc_s2_decode_blocks_all_dev", "kc_s2_decode_blocks_all", "kc_s2_decode_blocks_all_bound_dev", "kc_s2_decode_blocks_all_bound",
+    "kc_s2_index_new", "kc_s2_index_free", "kc_s2_index_load", "kc_s2_index_load_stream", "kc_s2_index_find", "kc_s2_index_total_uncompressed",
+    "kc_s2_index_total_compressed", "kc_s2_index_est_block_uncompressed", "kc_s2_index_entries", "kc_s2_index_stream",
+    "kc_s2_read_ranges_dev", "kc_s2_read_ranges",
     "kc_probe_table_pattern", "kc_probe_pcie", "kc_ctx_trim", "kc_device_trim", "kc_s2_hook_declined", "kc_create_error", "kc_host_alloc", "kc_host_free",
 ]
 
@@ -68,6 +72,29 @@ OPT_S2_HOOK_HOST_FIRST = 35
 _PATHS = {"auto": PATH_AUTO, "hbm": PATH_HBM, "lds": PATH_LDS, None: PATH_AUTO}
 
 _lib = None
+
+
+def declare_s2_index(L):
+    """ctypes signatures of the kc_s2_index_* functions (plain host code: any library that exports them)."""
+    vp, u64, i64 = C.c_void_p, C.c_uint64, C.c_int64
+    L.kc_s2_index_new.argtypes = []
+    L.kc_s2_index_new.restype = vp
+    L.kc_s2_index_free.argtypes = [vp]
+    L.kc_s2_index_free.restype = None
+    L.kc_s2_index_load.argtypes = [vp, vp, u64, C.POINTER(u64)]
+    L.kc_s2_index_load.restype = C.c_int
+    L.kc_s2_index_load_stream.argtypes = [vp, vp, u64]
+    L.kc_s2_index_load_stream.restype = C.c_int
+    L.kc_s2_index_find.argtypes = [vp, i64, C.POINTER(i64), C.POINTER(i64)]
+    L.kc_s2_index_find.restype = C.c_int
+    for n in ("total_uncompressed", "total_compressed", "est_block_uncompressed"):
+        f = getattr(L, "kc_s2_index_" + n)
+        f.argtypes = [vp]
+        f.restype = i64
+    L.kc_s2_index_entries.argtypes = [vp, vp, vp, C.c_uint32]
+    L.kc_s2_index_entries.restype = C.c_uint32
+    L.kc_s2_index_stream.argtypes = [vp, u64, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
+    L.kc_s2_index_stream.restype = C.c_int
 
 
 def lib_path():
@@ -211,6 +238,11 @@ def load():
     for n in ("kc_s2_decode_blocks_all_bound_dev", "kc_s2_decode_blocks_all_bound"):
         f = getattr(L, n)
         f.argtypes = [vp, vp, vp, C.c_uint32, vp, vp]
+        f.restype = C.c_int
+    declare_s2_index(L)
+    for n in ("kc_s2_read_ranges_dev", "kc_s2_read_ranges"):
+        f = getattr(L, n)
+        f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, u64, vp, vp, vp]
         f.restype = C.c_int
     L.kc_s2_encode_block.argtypes = [vp, vp, u64, vp, u64]
     L.kc_s2_encode_block.restype = C.c_int64

@@ -172,7 +172,8 @@ struct kc_ctx {
     bool job_primed = false;                // the units' tables start primed from their prefixes: by kc_zstd_prime_kernel, or from job_tables
     DevBuf d_job_hist, d_job_flags, rawdef, unit_raw;
     DevBuf zd[20];                       // zstd.Decoder.DecodeAll (kc_zstd_dec_api.cpp): plan, frame records, staging, literal scratch
-    DevBuf s2d[8];                       // s2.Reader / s2.Decode (kc_s2_dec_api.cpp): plan results, chunk records, chunk verdicts
+    DevBuf s2d[13];                      // s2.Reader / s2.Decode (kc_s2_dec_api.cpp): plan results, chunk records, chunk verdicts; from [8] on the
+                                         // ranged reads (kc_s2_ranges_api.cpp): requests, their plans, chunk records, verdicts, clip slots
     DevBuf unit_done, probe_rel;         // no-match pre-scan (kc_zstd_prescan.hip): per-unit verdicts; the probe positions of one block
     int probe_bs = 0;                    // block size probe_rel was built for
     uint32_t probe_n = 0;
@@ -198,6 +199,13 @@ struct kc_ctx {
 // (KC_ERR_UNSUPPORTED: the Go shim then calls the reference encoder).  s2.Writer never cuts blocks above 4 MiB (s2.maxBlockSize).
 #define KC_S2_MAX_BLOCK ((uint64_t)1 << 30)
 #define KC_S2_MAX_FRAMED_BLOCK ((uint64_t)4 << 20)  // s2.maxBlockSize: the largest block of a framed stream
+
+// the ReaderOptions behind kc_s2_ropts_* (kc_s2_dec_api.cpp), read by the whole-input and the ranged entry points
+struct kc_s2_ropts {
+    uint32_t max_block = (uint32_t)KC_S2_MAX_FRAMED_BLOCK;  // Reader.maxBlock (maxBlockSize)
+    int ignore_crc = 0;
+    int ignore_id = 0;
+};
 
 namespace kci {
 

@@ -291,7 +291,7 @@ struct KcZdDecodeParams {
 void kc_launch_zstd_decode_all(const KcZdDecodeParams& P, hipStream_t st);
 // ---- s2.Reader / s2.Decode as a product (kc_s2_plan_dev.h, kc_s2_plan.hip, kc_s2_decode_all.hip; host side kc_s2_dec_api.cpp) ----
 // Per-stream / per-chunk status classes (include/kcgpu.h KC_S2D_*)
-enum { KCS2D_OK = 0, KCS2D_CORRUPT = 1, KCS2D_CRC = 2, KCS2D_UNSUPPORTED = 3, KCS2D_SIZE = 4 };
+enum { KCS2D_OK = 0, KCS2D_CORRUPT = 1, KCS2D_CRC = 2, KCS2D_UNSUPPORTED = 3, KCS2D_SIZE = 4, KCS2D_EOF = 5, KCS2D_UNEXPECTED_EOF = 6 };
 #define KC_S2C_STORED 1u   // KcS2Chunk.kind: an uncompressed chunk (the body is the bytes), else a block (uvarint length + tags)
 #define KC_S2C_NOCRC 2u    // ... a bare block: nothing stored to compare with
 // One data chunk of one input, written by the plan kernel and consumed by the decode kernel.
@@ -331,6 +331,55 @@ struct KcS2DecodeAllParams {
     uint32_t* status;            // per chunk: KCS2D_OK / KCS2D_CORRUPT / KCS2D_CRC
 };
 void kc_launch_s2_decode_all(const KcS2DecodeAllParams& P, hipStream_t st);
+// ---- ranged reads of s2.ReadSeeker.ReadAt over a batch of requests (kc_s2_ranges.hip; host side kc_s2_ranges_api.cpp) ----
+#define KC_S2R_MID 1u      // KcS2Req.flags: the walk starts at an index entry, behind the identifier at the input's front
+#define KC_S2R_SNAPPY 2u   // ... whose identifier was Snappy's (the host looked); without KC_S2R_KNOWN the lane looks at `front` itself
+#define KC_S2R_KNOWN 4u
+#define KC_S2R_NO_SLOT (~0ull)
+// One request: decoded bytes [off, off + len) of the input [front, end) of src, walked from `pos` where `u` decoded bytes lie in front.
+struct KcS2Req {
+    uint64_t front, end;         // the input in src
+    uint64_t pos;                // where the walk starts: front, or front + the index entry's compressed offset
+    uint64_t u;                  // decoded offset at pos
+    uint64_t off, len;           // the range
+    uint64_t out0;               // second pass: where the request's range starts in dst
+    uint64_t slot0;              // second pass: where its scratch slots start
+    uint32_t chunk0;             // second pass: index of its first record
+    uint32_t flags;              // KC_S2R_*
+};
+struct KcS2ReqPlan {             // first pass, per request
+    uint64_t got;                // min(len, bytes available from off)
+    uint64_t slot_bytes;         // scratch its clipped chunks take (each dlen rounded up to 16; at most two chunks)
+    uint32_t n_chunks;           // covered chunks
+    uint32_t status;             // first header-level error, KCS2D_EOF, KCS2D_UNEXPECTED_EOF
+};
+// One covered chunk.  A chunk wholly inside its request decodes to c.out_off in dst; a clipped one decodes to its slot and the
+// bytes [clip_lo, clip_hi) of it are copied to c.out_off.  c.stream is the request, c.index the chunk's number among its covered chunks.
+struct KcS2RChunk {
+    KcS2Chunk c;
+    uint64_t slot_off;           // KC_S2R_NO_SLOT: not clipped
+    uint32_t clip_lo, clip_hi;   // relative to the chunk
+};
+struct KcS2RangePlanParams {
+    const uint8_t* src;
+    KcS2Req* reqs;               // device, m (the second pass reads out0 / slot0 / chunk0)
+    uint32_t m;
+    uint32_t max_block, max_buf;
+    int32_t ignore_id;
+    KcS2ReqPlan* plan;           // first pass (chunks == null)
+    KcS2RChunk* chunks;          // second pass
+};
+void kc_launch_s2_range_plan(const KcS2RangePlanParams& P, hipStream_t st);
+struct KcS2RangeDecodeParams {
+    const uint8_t* src;
+    const KcS2RChunk* chunks;
+    uint32_t n_chunks;
+    uint8_t* dst;
+    uint8_t* slots;
+    int32_t ignore_crc;
+    uint32_t* status;            // per covered chunk: KCS2D_OK / KCS2D_CORRUPT / KCS2D_CRC
+};
+void kc_launch_s2_range_decode(const KcS2RangeDecodeParams& P, hipStream_t st);
 // default: 2^14 entries; better: long 2^17 + short 2^14 (blocks > 64 KiB), long 2^16 + short 2^13 (all blocks <= 64 KiB)
 static inline size_t kc_s2_table_bytes(int level, uint64_t max_block_len, int variant = 0) {
     // the assembly forms of the better levels take 2^17 + 2^14 entries from 16 KiB on (Snappy-compatible: above 64 KiB; 2^16 + 2^13 below)

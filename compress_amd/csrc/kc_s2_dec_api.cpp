@@ -9,12 +9,6 @@
 #include "kc_host.h"
 #include "kc_s2_plan_dev.h"
 
-struct kc_s2_ropts {
-    uint32_t max_block = (uint32_t)KC_S2_MAX_FRAMED_BLOCK;  // Reader.maxBlock (maxBlockSize)
-    int ignore_crc = 0;
-    int ignore_id = 0;
-};
-
 namespace {
 
 enum { SD_IN_OFF, SD_NC, SD_BOUND, SD_STATUS, SD_CHUNK0, SD_OUT0, SD_CHUNKS, SD_CSTATUS };  // c->s2d[]

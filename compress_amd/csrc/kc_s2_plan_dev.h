@@ -30,16 +30,20 @@ struct KcS2Walk {
     uint32_t status;    // the first header-level error (KCS2D_*), 0: the walk reached the input's end at a chunk boundary
     uint32_t n_chunks;  // data chunks in front of it
     uint64_t total;     // their decoded bytes
+    uint32_t stopped;   // kc_s2_walk_from: more() ended the walk in front of the input's end
 };
 
-// emit(index, body_off, body_len, kind, out_rel, dlen, crc) is called for every data chunk in stream order.
-template <class Emit>
-__host__ __device__ inline KcS2Walk kc_s2_walk(const uint8_t* in, uint64_t pos, const uint64_t end, uint32_t max_block, uint32_t max_buf, bool ignore_id,
-                                               Emit emit) {
+// The walk from a given reader state: readHeader / snappy are Reader.readHeader / Reader.snappyFrame at `pos` (a chunk boundary).
+// more(total) is asked before every chunk header is read: false ends the walk there with status 0 and W.stopped set — nothing at
+// or behind `pos` has been read then (the ranged plan, kc_s2_ranges.hip).  emit(index, body_off, body_len, kind, out_rel, dlen, crc)
+// is called for every data chunk in stream order.
+template <class More, class Emit>
+__host__ __device__ inline KcS2Walk kc_s2_walk_from(const uint8_t* in, uint64_t pos, const uint64_t end, uint32_t max_block, uint32_t max_buf,
+                                                    bool readHeader, bool snappy, More more, Emit emit) {
     KcS2Walk W;
-    W.status = KCS2D_OK; W.n_chunks = 0; W.total = 0;
-    bool readHeader = ignore_id, snappy = false;
+    W.status = KCS2D_OK; W.n_chunks = 0; W.total = 0; W.stopped = 0;
     while (pos < end) {  // (nothing left: io.EOF from the 4-byte read, the clean end)
+        if (!more(W.total)) { W.stopped = 1; break; }
         if (end - pos < 4) { W.status = KCS2D_CORRUPT; break; }
         const uint32_t type = in[pos];
         const uint32_t chunkLen = (uint32_t)in[pos + 1] | ((uint32_t)in[pos + 2] << 8) | ((uint32_t)in[pos + 3] << 16);
@@ -77,4 +81,57 @@ __host__ __device__ inline KcS2Walk kc_s2_walk(const uint8_t* in, uint64_t pos, 
         pos += chunkLen;
     }
     return W;
+}
+
+// emit(index, body_off, body_len, kind, out_rel, dlen, crc) is called for every data chunk in stream order.
+template <class Emit>
+__host__ __device__ inline KcS2Walk kc_s2_walk(const uint8_t* in, uint64_t pos, const uint64_t end, uint32_t max_block, uint32_t max_buf, bool ignore_id,
+                                               Emit emit) {
+    return kc_s2_walk_from(in, pos, end, max_block, max_buf, ignore_id, false, [](uint64_t) { return true; }, emit);
+}
+
+// The reader's state behind the stream identifier at the front of the input [front, end): what a ranged read that starts in the
+// middle of the input (at an index entry) starts from.  Without a valid identifier there the reader would have refused the input
+// before it could seek (reader.go:263-269) unless it ignores identifiers.
+__host__ __device__ inline uint32_t kc_s2_front_state(const uint8_t* in, uint64_t front, uint64_t end, bool ignore_id, bool* snappy) {
+    *snappy = false;
+    if (end >= front && end - front >= 10 && in[front] == 0xffu && in[front + 1] == 6 && in[front + 2] == 0 && in[front + 3] == 0) {
+        const uint8_t* m = in + front + 4;
+        if (m[0] == 'S' && m[1] == '2' && m[2] == 's' && m[3] == 'T' && m[4] == 'w' && m[5] == 'O') return KCS2D_OK;
+        if (m[0] == 's' && m[1] == 'N' && m[2] == 'a' && m[3] == 'P' && m[4] == 'p' && m[5] == 'Y') { *snappy = true; return KCS2D_OK; }
+    }
+    return ignore_id ? KCS2D_OK : KCS2D_CORRUPT;
+}
+
+// One request of a ranged read: its walk.  The lane stands at `pos` (the stream's start, or the index entry Find gave) where `u`
+// decoded bytes lie in front of it, and wants [off, off + len).  A chunk that ends at or before off while the reader is still
+// skipping (its start lies in front of off) is passed by its header alone; every chunk from the one that holds off onwards is
+// covered: cover(index, body_off, body_len, kind, a, dlen, crc) with `a` its decoded start in the stream.  The walk ends once the
+// decoded position has reached off + len (for len 0: off) and reads nothing behind that point.
+struct KcS2RangeWalk {
+    uint32_t status;   // header-level error, KCS2D_EOF (the input ended inside the range) or KCS2D_UNEXPECTED_EOF (in front of it)
+    uint32_t n_cover;  // covered chunks
+    uint64_t got;      // min(len, decoded bytes available from off)
+};
+template <class Cover>
+__host__ __device__ inline KcS2RangeWalk kc_s2_walk_range(const uint8_t* in, uint64_t pos, uint64_t end, uint32_t max_block, uint32_t max_buf,
+                                                          bool readHeader, bool snappy, uint64_t u, uint64_t off, uint64_t len, Cover cover) {
+    KcS2RangeWalk R;
+    R.n_cover = 0;
+    uint32_t n_cover = 0;
+    auto more = [&](uint64_t total) { const uint64_t cur = u + total; return cur < off || cur - off < len; };
+    auto emit = [&](uint32_t, uint64_t body_off, uint32_t body_len, uint32_t kind, uint64_t out_rel, uint32_t dlen, uint32_t crc) {
+        const uint64_t a = u + out_rel;
+        if (a < off && a + dlen <= off) return;  // Skip: "CRC is not checked on skipped blocks" (reader.go:671)
+        cover(n_cover, body_off, body_len, kind, a, dlen, crc);
+        n_cover++;
+    };
+    if (pos > end) pos = end;
+    const KcS2Walk W = kc_s2_walk_from(in, pos, end, max_block, max_buf, readHeader, snappy, more, emit);
+    const uint64_t cur = u + W.total;
+    R.n_cover = n_cover;
+    R.status = W.status;
+    R.got = cur <= off ? 0 : (cur - off < len ? cur - off : len);
+    if (!W.status && !W.stopped && more(W.total)) R.status = cur < off ? KCS2D_UNEXPECTED_EOF : KCS2D_EOF;  // Skip / ReadAt at the input's end
+    return R;
 }

@@ -236,12 +236,84 @@ def calc_skippable_frame(written, want_multiple):
 
 
 class Index:
-    """The writer side of s2.Index (s2/index.go:17-236): add / reduce / appendTo."""
+    """s2.Index (s2/index.go).  The writer side — add / reduce / appendTo (:17-236) — is Python; the reader side — Load, LoadStream,
+    Find (:97-127, 238-413) — runs in the library's host code (kc_s2_index.cpp), which checks every read of the untrusted bytes."""
     MAX_ENTRIES, MIN_DIST = 1 << 16, 1 << 20
 
-    def __init__(self, max_block):
+    def __init__(self, max_block=0):
         self.est = int(max_block)
         self.info = []  # [compressedOffset, uncompressedOffset]
+        self.TotalUncompressed = -1
+        self.TotalCompressed = -1
+        self._h = None
+
+    def _adopt(self, h, rc):
+        L = _lib.load()
+        if rc:
+            L.kc_s2_index_free(h)
+            raise S2DecodeError(rc)
+        import numpy as np
+        n = L.kc_s2_index_entries(h, None, None, 0)
+        c, u = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64)
+        L.kc_s2_index_entries(h, c.ctypes.data, u.ctypes.data, n)
+        self.info = [[int(c[k]), int(u[k])] for k in range(n)]
+        self.TotalUncompressed = int(L.kc_s2_index_total_uncompressed(h))
+        self.TotalCompressed = int(L.kc_s2_index_total_compressed(h))
+        self.est = int(L.kc_s2_index_est_block_uncompressed(h))
+        self._drop()
+        self._h = C.c_void_p(h)
+
+    def _drop(self):
+        h, self._h = self._h, None
+        if h:
+            _lib.load().kc_s2_index_free(h)
+
+    def __del__(self):
+        try:
+            self._drop()
+        except Exception:
+            pass
+
+    def Load(self, b):
+        """Index.Load (index.go:238): read a binary index from the front of b and return the rest.  Raises S2DecodeError with the class
+        of the reference's error (KC_S2D_UNEXPECTED_EOF, KC_S2D_CORRUPT, KC_S2D_UNSUPPORTED)."""
+        b = bytes(b)
+        L = _lib.load()
+        h = L.kc_s2_index_new()
+        used = C.c_uint64(0)
+        self._adopt(h, L.kc_s2_index_load(h, b, len(b), C.byref(used)))
+        return b[used.value:]
+
+    def LoadStream(self, stream):
+        """Index.LoadStream (index.go:381) over the bytes of a whole stream: the index is looked for at its end."""
+        stream = bytes(stream)
+        L = _lib.load()
+        h = L.kc_s2_index_new()
+        self._adopt(h, L.kc_s2_index_load_stream(h, stream, len(stream)))
+
+    def _handle(self):
+        """The library's copy of this index (made by Load / LoadStream, else from the bytes appendTo would write)."""
+        if self._h is None:
+            w = Index(self.est)
+            w.info = [list(e) for e in self.info]
+            self.Load(w.append_to(self.TotalUncompressed, self.TotalCompressed))
+        return self._h
+
+    def Find(self, offset):
+        """Index.Find (index.go:97): (compressed offset, uncompressed offset) of the entry at or before `offset`; a negative offset counts
+        from the end.  Raises S2DecodeError (KC_S2D_UNEXPECTED_EOF outside the stream, KC_S2D_CORRUPT without a known total)."""
+        c, u = C.c_int64(0), C.c_int64(0)
+        rc = _lib.load().kc_s2_index_find(self._handle(), int(offset), C.byref(c), C.byref(u)) if self.TotalUncompressed >= 0 else 1
+        if rc:
+            raise S2DecodeError(rc)
+        return c.value, u.value
+
+    def JSON(self):
+        """Index.JSON (index.go:519): the index as JSON text, in the reference's field names and two-space indent."""
+        import json
+        x = {"total_uncompressed": self.TotalUncompressed, "total_compressed": self.TotalCompressed,
+             "offsets": [{"compressed": c, "uncompressed": u} for c, u in self.info] or None, "est_block_uncompressed": self.est}
+        return json.dumps(x, indent=2).encode()
 
     def add(self, comp, unc):
         if self.info:
@@ -511,8 +583,8 @@ def NewWriter(w, *opts, **kw):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # s2.Reader / s2.Decode (s2/reader.go, s2/decode.go) over the device path: whole inputs, in batches.  Every input is decoded
-# as io.ReadAll(s2.NewReader(input)) would; the sequential interface (Read, Skip, ReadSeeker, ReadByte) and skippable-chunk
-# callbacks stay with the reference.
+# as io.ReadAll(s2.NewReader(input)) would; ranged reads go through Reader.ReadRanges and the cursor s2.NewReadSeeker returns.
+# The methods Read, Skip, ReadSeeker, ReadByte of Reader itself and skippable-chunk callbacks stay with the reference.
 # ---------------------------------------------------------------------------------------------------------------------
 class S2DecodeError(ValueError):
     """The reader refused an input.  `name` is the class of the reference's error: KC_S2D_CORRUPT (ErrCorrupt), KC_S2D_CRC (ErrCRC),
@@ -673,6 +745,57 @@ class Reader:
         """DecodeBlocks over device-resident blocks (kc_s2_decode_blocks_all_dev): (uint64[n+1] offsets, uint32[n] status)."""
         return self._dev("kc_s2_decode_blocks_all_dev", False, d_src_ptr, in_off, d_dst_ptr, dst_cap)
 
+    def _ranges(self, fn, src_ptr, in_off, requests, indexes, dst_ptr, dst_cap):
+        import numpy as np
+        ctx = self.ctx()
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        ns = len(in_off) - 1
+        m = len(requests)
+        rs = np.ascontiguousarray([r[0] for r in requests] + [0], dtype=np.uint32)
+        ro = np.ascontiguousarray([r[1] for r in requests] + [0], dtype=np.uint64)
+        rl = np.ascontiguousarray([r[2] for r in requests] + [0], dtype=np.uint64)
+        keep = []
+        ix = None
+        if indexes is not None:
+            if len(indexes) != ns:
+                raise ValueError("s2: one index (or None) per input")
+            ix = (C.c_void_p * max(ns, 1))()
+            for k, i in enumerate(indexes):
+                if i is None:
+                    continue
+                if not isinstance(i, Index):  # the bytes of an index
+                    b, i = i, Index()
+                    i.Load(b)
+                keep.append(i)
+                ix[k] = i._handle()
+        out_off = np.zeros(m + 1, dtype=np.uint64)
+        got = np.zeros(max(m, 1), dtype=np.uint64)
+        status = np.zeros(max(m, 1), dtype=np.uint32)
+        ctx.check(getattr(ctx.L, fn)(ctx.h, self._o, src_ptr, in_off.ctypes.data, ns, ix, rs.ctypes.data, ro.ctypes.data, rl.ctypes.data, m, dst_ptr,
+                                     int(dst_cap), out_off.ctypes.data, got.ctypes.data, status.ctypes.data))
+        return out_off, got[:m], status[:m]
+
+    def ReadRangesDevice(self, d_src_ptr, in_off, requests, d_dst_ptr, dst_cap, indexes=None):
+        """N x ReadSeeker.ReadAt over device-resident inputs (kc_s2_read_ranges_dev).  requests: (input, offset, length) triples;
+        indexes: per input an Index, the bytes of one, or None (the input is then walked from its start).  Request j owns
+        d_dst[out_off[j]:out_off[j + 1]], out_off being the prefix sum of the lengths.  Returns (out_off uint64[m + 1], got uint64[m],
+        status uint32[m]); status KC_S2D_EOF is a short read (got < length, the rest zero-filled), any other non-zero status leaves
+        the range zero-filled.  Raises KcError KC_ERR_DST_TOO_SMALL when the lengths do not fit dst_cap (nothing is written)."""
+        return self._ranges("kc_s2_read_ranges_dev", d_src_ptr, in_off, requests, indexes, d_dst_ptr, dst_cap)
+
+    def ReadRanges(self, src, in_off, requests, indexes=None):
+        """ReadRangesDevice over host buffers (kc_s2_read_ranges): per request only the compressed bytes its index entry points at are
+        staged.  Returns a list with, per request, (bytes, status): the bytes it got (fewer than asked for with KC_S2D_EOF, b"" with
+        any other non-zero status)."""
+        import numpy as np
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        if len(src) == 0:
+            src = np.zeros(1, dtype=np.uint8)
+        cap = sum(int(r[2]) for r in requests)
+        dst = np.empty(cap + 64, dtype=np.uint8)
+        out_off, got, status = self._ranges("kc_s2_read_ranges", src.ctypes.data, in_off, requests, indexes, dst.ctypes.data, cap)
+        return [(dst[int(out_off[j]):int(out_off[j]) + int(got[j])].tobytes(), int(status[j])) for j in range(len(requests))]
+
     def Read(self, p):
         _unsupported("Reader.Read", "reader")()(self)
 
@@ -704,6 +827,143 @@ class Reader:
 def NewReader(r, *opts, **kw):
     """s2.NewReader(r, opts...) (reader.go:31)."""
     return Reader(r, *opts, **kw)
+
+
+def IndexStream(r):
+    """s2.IndexStream (index.go:420): the index of a stream, built from its chunk headers on the host; it can be appended to the stream
+    or kept beside it.  r: bytes or a reader.  Raises S2DecodeError with the class of the reference's error."""
+    data = r.read() if hasattr(r, "read") else bytes(r)
+    L = _lib.load()
+    cap = 64 + 20 * (len(data) // (1 << 20) + 2)
+    while True:
+        out = C.create_string_buffer(cap)
+        n, st = C.c_uint64(0), C.c_uint32(0)
+        rc = L.kc_s2_index_stream(data, len(data), out, cap, C.byref(n), C.byref(st))
+        if rc == _lib.KC_ERR_DST_TOO_SMALL:
+            cap = int(n.value)
+            continue
+        if rc:
+            raise _lib.KcError(rc, "kc_s2_index_stream")
+        if st.value:
+            raise S2DecodeError(st.value)
+        return out.raw[:n.value]
+
+
+class ErrCantSeek(ValueError):
+    """s2.ErrCantSeek (reader.go): the reader cannot give random access; `Reason` says why."""
+
+    def __init__(self, reason):
+        self.Reason = reason
+        super().__init__("s2: Can't seek because " + reason)
+
+
+SeekStart, SeekCurrent, SeekEnd = 0, 1, 2
+
+
+class ReadSeeker:
+    """s2.ReadSeeker (reader.go:844-1041) over the whole input held in r: a cursor over Reader.ReadRanges.  Seek / Read / ReadAt / Skip /
+    ReadByte; every read decodes on the device only the chunks that hold its range, starting from the index entry in front of it.
+    random=False (or no index): forward-only — the input is walked from its start and a backward Seek is refused."""
+
+    def __init__(self, r, *opts, random=True, index=None, device=0, stream=None):
+        import numpy as np
+        data = r.read() if hasattr(r, "read") else bytes(r)
+        self._src = np.frombuffer(data, dtype=np.uint8)
+        self._off = np.array([0, len(data)], dtype=np.uint64)
+        self._rd = Reader(None, *opts, device=device, stream=stream)
+        self._pos = 0
+        self._index = None
+        if index is not None and len(index) != 0:  # a supplied index wins (reader.go:866-873)
+            self._index = Index()
+            try:
+                self._index.Load(index)
+            except S2DecodeError as e:
+                raise ErrCantSeek("loading index returned: " + str(e))
+        else:
+            ix = Index()
+            try:
+                ix.LoadStream(data)
+                self._index = ix
+            except S2DecodeError as e:
+                if e.name != "KC_S2D_UNSUPPORTED":
+                    raise ErrCantSeek("reading index returned: " + str(e))
+                if random:
+                    raise ErrCantSeek("input stream does not contain an index")
+
+    def _read(self, off, n):
+        """(bytes, status) of ReadAt(n bytes, off) without moving the cursor."""
+        return self._rd.ReadRanges(self._src, self._off, [(0, off, n)], None if self._index is None else [self._index])[0]
+
+    def Seek(self, offset, whence=SeekStart):
+        """ReadSeeker.Seek (reader.go:923): returns the new absolute offset."""
+        if whence == SeekStart:
+            a = offset
+        elif whence == SeekCurrent:
+            a = self._pos + offset
+        elif whence == SeekEnd:
+            if self._index is None:
+                raise S2DecodeError(3)  # ErrUnsupported (reader.go:941)
+            a = self._index.TotalUncompressed + offset
+        else:
+            raise S2DecodeError(3)
+        if a < 0:
+            raise ValueError("seek before start of file")
+        if self._index is None and a < self._pos:
+            raise S2DecodeError(3)  # forward-only (reader.go:975)
+        _, st = self._read(a, 0)  # the chunk that holds the target is decoded and checked, as Skip does
+        if st:
+            raise S2DecodeError(st)
+        self._pos = a
+        return a
+
+    def ReadAt(self, p, off):
+        """ReadSeeker.ReadAt (reader.go:1024): fills p from offset off; returns the bytes read.  A short read at the input's end returns
+        what there is (the reference returns it with io.EOF); the cursor moves to the end of what was read (reader.go:859)."""
+        if off < 0:
+            raise ValueError("seek before start of file")
+        if self._index is None and off < self._pos:
+            raise S2DecodeError(3)
+        b, st = self._read(off, len(p))
+        if st and st != 5:
+            raise S2DecodeError(st)
+        p[:len(b)] = b
+        self._pos = off + len(b)
+        return len(b)
+
+    def Read(self, p):
+        """io.Reader: up to len(p) bytes from the cursor; 0 at the end of the input."""
+        b, st = self._read(self._pos, len(p))
+        if st and st != 5:
+            raise S2DecodeError(st)
+        p[:len(b)] = b
+        self._pos += len(b)
+        return len(b)
+
+    def Skip(self, n):
+        """Reader.Skip (reader.go:674): n decoded bytes forward; KC_S2D_UNEXPECTED_EOF when the input ends first."""
+        if n < 0:
+            raise ValueError("attempted negative skip")
+        _, st = self._read(self._pos + n, 0)
+        if st:
+            raise S2DecodeError(st)
+        self._pos += n
+
+    def ReadByte(self):
+        """Reader.ReadByte (reader.go:1044); raises EOFError at the end of the input."""
+        p = bytearray(1)
+        if self.Read(p) != 1:
+            raise EOFError("EOF")
+        return p[0]
+
+    def Close(self):
+        self._rd.Close()
+
+
+def NewReadSeeker(r, *opts, random=True, index=None, **kw):
+    """s2.NewReader(r, opts...).ReadSeeker(random, index) (reader.go:864-920) as one constructor: r holds the whole input.  A supplied
+    index is used and none is read from the input; otherwise the index at the input's end is loaded.  Without one, random=True raises
+    ErrCantSeek and random=False gives a forward-only seeker."""
+    return ReadSeeker(r, *opts, random=random, index=index, **kw)
 
 
 _decoders = {}

@@ -416,7 +416,9 @@ enum {
     KC_S2D_CORRUPT = 1,        /* ErrCorrupt */
     KC_S2D_CRC = 2,            /* ErrCRC */
     KC_S2D_UNSUPPORTED = 3,    /* ErrUnsupported */
-    KC_S2D_SIZE_EXCEEDED = 4   /* a limit of this library: host-buffer calls, an input that does not fit the scratch ceiling alone */
+    KC_S2D_SIZE_EXCEEDED = 4,  /* a limit of this library: host-buffer calls, an input that does not fit the scratch ceiling alone */
+    KC_S2D_EOF = 5,            /* ranged reads: io.EOF — the input ended inside the range, got < len */
+    KC_S2D_UNEXPECTED_EOF = 6  /* ranged reads: io.ErrUnexpectedEOF — the input ended in front of the range (Reader.Skip, Index.Find) */
 };
 /* kc_s2_decode_streams[_dev] == io.ReadAll(s2.NewReader(input, options)) for every input (s2/reader.go:249-405).  src: the inputs,
  * concatenated; in_off: n + 1 ascending offsets into it.  Input i is any concatenation of .s2 or Snappy-framed streams, as
@@ -456,6 +458,71 @@ kc_status kc_s2_decode_blocks_all_bound_dev(kc_ctx* ctx, const uint8_t* d_src, c
                                             uint32_t* status);
 kc_status kc_s2_decode_blocks_all_bound(kc_ctx* ctx, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint64_t* bound,
                                         uint32_t* status);
+/* ---- s2.Index and ranged reads: Index.Load / LoadStream / Find, IndexStream, ReadSeeker.ReadAt over a batch of requests ----
+ * (s2/index.go, s2/reader.go:669-1041)
+ *
+ * The index on the host (plain C++, no device): a kc_s2_index holds what s2.Index holds — the totals, the block size estimate and the
+ * (compressed offset, uncompressed offset) entries.  Every read of index bytes is bounds-checked; the results are the reference's:
+ * KC_S2I_UNEXPECTED_EOF == io.ErrUnexpectedEOF, KC_S2I_CORRUPT == ErrCorrupt, KC_S2I_UNSUPPORTED == ErrUnsupported, returned at the
+ * places where Index.Load (index.go:238-374), Index.LoadStream (:381-413, over a buffer: a missing trailer is KC_S2I_UNSUPPORTED,
+ * fewer than 10 bytes: the reference's Seek fails; here KC_S2I_UNEXPECTED_EOF) and Index.Find (:97-127; negative offsets
+ * count from the end, an offset behind the end is KC_S2I_UNEXPECTED_EOF) return them.  The numbers equal the KC_S2D_* classes.
+ * kc_s2_index_load: *consumed (may be null) = the bytes of b in front of the rest Index.Load returns.  Like the reference, a failed
+ * load leaves the index partly overwritten.  kc_s2_index_entries copies up to cap entries and returns the entry count.
+ * kc_s2_index_stream == s2.IndexStream (:420-516): walks the chunk headers of src and writes the index chunk Index.appendTo builds
+ * to out (cap bytes; KC_ERR_DST_TOO_SMALL with *out_len = the bytes needed).  *status = 0 or the class of the reference's error
+ * (nothing is written then).  Its checks are IndexStream's own, not the Reader's: chunkLen < 4 is corrupt for every chunk type and
+ * the block limit is maxBlockSize (4 MiB) whatever a reader would be told. */
+enum { KC_S2I_OK = 0, KC_S2I_CORRUPT = 1, KC_S2I_UNSUPPORTED = 3, KC_S2I_UNEXPECTED_EOF = 6 };
+typedef struct kc_s2_index kc_s2_index;
+kc_s2_index* kc_s2_index_new(void);
+void kc_s2_index_free(kc_s2_index* ix);
+int kc_s2_index_load(kc_s2_index* ix, const uint8_t* b, uint64_t n, uint64_t* consumed);
+int kc_s2_index_load_stream(kc_s2_index* ix, const uint8_t* stream, uint64_t n);
+int kc_s2_index_find(const kc_s2_index* ix, int64_t offset, int64_t* c_off, int64_t* u_off);
+int64_t kc_s2_index_total_uncompressed(const kc_s2_index* ix);
+int64_t kc_s2_index_total_compressed(const kc_s2_index* ix);
+int64_t kc_s2_index_est_block_uncompressed(const kc_s2_index* ix);
+uint32_t kc_s2_index_entries(const kc_s2_index* ix, int64_t* c_off, int64_t* u_off, uint32_t cap);
+kc_status kc_s2_index_stream(const uint8_t* src, uint64_t n, uint8_t* out, uint64_t cap, uint64_t* out_len, uint32_t* status);
+/* kc_s2_read_ranges[_dev] == for every request j: s2.NewReader(input req_stream[j], options).ReadSeeker(true, index).ReadAt(p, req_off[j])
+ * with len(p) == req_len[j], as one batch.  src / in_off / n_streams: the inputs as for kc_s2_decode_streams.  index: n_streams
+ * pointers (the array itself may be null), a null entry = no index: the request is then served by walking the input from its start
+ * (Reader.Skip), otherwise from the entry Index.Find gives for req_off[j].  All arrays are HOST arrays; src / dst are device memory
+ * for _dev, host memory otherwise.
+ *
+ * Layout: request j owns dst[out_off[j], out_off[j + 1]) with out_off the prefix sum of req_len (m + 1 entries), whatever the data
+ * holds.  KC_ERR_DST_TOO_SMALL when out_off[m] > dst_cap, before anything is written; KC_ERR_BAD_ARG for a request that names an input
+ * >= n_streams or whose off + len wraps.  status[j] / got[j]:
+ *   KC_S2D_OK               got == len.
+ *   KC_S2D_EOF              the input ended inside the range: got < len bytes stand at the front of the request's range, the rest
+ *                           is zero-filled (ReadAt: n < len(p), io.EOF).
+ *   KC_S2D_UNEXPECTED_EOF   the input ended in front of off (Skip), or Index.Find refused off; got == 0.
+ *   any other class         the first failing covered chunk in stream order, else the first header-level error of the walk; got == 0.
+ * Whenever got == 0 by an error the request's whole range is zero-filled.  A request whose Find fails never reaches the device.
+ *
+ * What is read: the chunk headers from the walk's start up to the chunk whose decoded end reaches off + len, and the bodies of the
+ * chunks from the one that holds off onwards (the covered chunks; their CRCs are checked over the whole chunk).  Chunks in front of
+ * off are passed by their headers alone — chunk type, chunk length, DecodedLen and the block size limits are checked, bodies and
+ * CRCs are not ("CRC is not checked on skipped blocks", reader.go:671) — and nothing behind the last covered chunk is read.  For
+ * len == 0 the chunk that holds off is still decoded and checked, unless off is a chunk's end (or the walk's start).
+ * A walk that starts at an index entry starts in the state the reader has behind the stream identifier at the input's front: an
+ * input without one is KC_S2D_CORRUPT unless identifiers are ignored.
+ * Differences from the reference, on purpose: (1) Reader.Skip CRC-checks an UNCOMPRESSED chunk it passes when the chunk is shorter
+ * than what is left to skip (reader.go:799); here no skipped chunk's body is read.  (2) The reference's first Seek decodes the first
+ * data chunk of the input before it seeks (reader.go:953-959); here the front is read for its identifier only.  (3) Skip does not
+ * apply Snappy's 64 KiB limit to the chunks it passes; the walk here does, as for every chunk.
+ *
+ * Host-buffer form: per request only the compressed bytes from its index entry up to the first entry at or above off + len (the
+ * input's end without an index, or behind the last entry) are staged, in groups whose staged bytes and lengths fit a quarter of
+ * the scratch ceiling; a request that does not fit alone gets KC_S2D_SIZE_EXCEEDED and a zero-filled range.  An index that lies
+ * about where chunks start can so turn into KC_S2D_CORRUPT / KC_S2D_EOF where the device-resident form would read on. */
+kc_status kc_s2_read_ranges_dev(kc_ctx* ctx, const kc_s2_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n_streams,
+                                const kc_s2_index* const* index, const uint32_t* req_stream, const uint64_t* req_off, const uint64_t* req_len,
+                                uint32_t m, uint8_t* d_dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* got, uint32_t* status);
+kc_status kc_s2_read_ranges(kc_ctx* ctx, const kc_s2_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n_streams,
+                            const kc_s2_index* const* index, const uint32_t* req_stream, const uint64_t* req_off, const uint64_t* req_len,
+                            uint32_t m, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* got, uint32_t* status);
 /* Single-block form with the WriterCustomEncoder contract (s2/writer.go:1053-1064): no varint header;
  * returns bytes used, 0 = incompressible (store raw), <0 = fall back to the built-in encoder.
  * "The function should expect to be called concurrently" (writer.go:1058; s2.Writer calls it from one goroutine per block,

@@ -20,6 +20,8 @@
 #include "../../compress_amd/csrc/kc_zdec_host.h"
 #include "../../compress_amd/csrc/kc_s2_plan.hip"
 #include "../../compress_amd/csrc/kc_s2_decode_all.hip"
+#include "../../compress_amd/csrc/kc_s2_ranges.hip"
+#include "../../compress_amd/csrc/kc_s2_index.cpp"   // (host code: s2.Index, exported from this library as from the product)
 
 // s2.Reader / s2.Decode over n inputs on the emulator: the plan kernel (both passes), the decode kernel with its CRC, the verdict per
 // input (first failing chunk in stream order, else the plan's error) and the zero-fill of the failed ranges — kc_s2_dec_api.cpp's
@@ -134,6 +136,75 @@ int kcemu_s2_decode_streams(const uint8_t* src, const uint64_t* in_off, uint32_t
     memset(&P, 0, sizeof(P));
     P.src = src; P.in_off = in_off; P.n = n; P.max_block = max_block; P.max_buf = max_buf; P.ignore_id = ignore_id;
     return kcemu_s2_decode(P, ignore_crc, dst, dst_cap, out_off, bound, status);
+}
+
+// s2.ReadSeeker.ReadAt over m requests on the emulator: Index.Find per request, the ranged plan (both passes), the clipped decode,
+// the verdict per request and the zero-fills — kc_s2_ranges_api.cpp's sequence as one batch in plain memory.  Returns 0, -2 when
+// dst_cap is too small (nothing written), -1 for a request that names no input or wraps.
+int kcemu_s2_read_ranges(const uint8_t* src, const uint64_t* in_off, uint32_t n_streams, const kc_s2_index* const* index, const uint32_t* req_stream,
+                         const uint64_t* req_off, const uint64_t* req_len, uint32_t m, uint32_t max_block, uint32_t max_buf, int ignore_crc, int ignore_id,
+                         uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* got, uint32_t* status) {
+    out_off[0] = 0;
+    for (uint32_t j = 0; j < m; j++) {
+        if (req_stream[j] >= n_streams || req_off[j] + req_len[j] < req_off[j]) return -1;
+        out_off[j + 1] = out_off[j] + req_len[j];
+    }
+    if (out_off[m] > dst_cap) return -2;
+    std::vector<KcS2Req> Q;
+    std::vector<uint32_t> live;
+    for (uint32_t j = 0; j < m; j++) {
+        const uint32_t s = req_stream[j];
+        KcS2Req q;
+        memset(&q, 0, sizeof(q));
+        q.front = in_off[s]; q.end = in_off[s + 1]; q.pos = q.front; q.off = req_off[j]; q.len = req_len[j]; q.out0 = out_off[j];
+        if (index && index[s]) {
+            int64_t cc = 0, uu = 0;
+            const int rc = q.off > (uint64_t)INT64_MAX ? (int)KC_S2I_UNEXPECTED_EOF : kc_s2_index_find(index[s], (int64_t)q.off, &cc, &uu);
+            if (rc) {
+                status[j] = (uint32_t)rc; got[j] = 0;
+                if (q.len) memset(dst + out_off[j], 0, (size_t)q.len);
+                continue;
+            }
+            if (cc > 0) { q.pos = (uint64_t)cc > q.end - q.front ? q.end : q.front + (uint64_t)cc; q.flags = KC_S2R_MID; }
+            q.u = (uint64_t)uu;
+        }
+        live.push_back(j);
+        Q.push_back(q);
+    }
+    const uint32_t n = (uint32_t)Q.size();
+    if (n == 0) return 0;
+    std::vector<KcS2ReqPlan> H(n);
+    KcS2RangePlanParams P;
+    memset(&P, 0, sizeof(P));
+    P.src = src; P.reqs = Q.data(); P.m = n; P.max_block = max_block; P.max_buf = max_buf; P.ignore_id = ignore_id; P.plan = H.data();
+    kc_launch_s2_range_plan(P, nullptr);
+    uint32_t nc = 0;
+    uint64_t slots = 0;
+    for (uint32_t i = 0; i < n; i++) { Q[i].chunk0 = nc; Q[i].slot0 = slots; nc += H[i].n_chunks; slots += H[i].slot_bytes; }
+    std::vector<KcS2RChunk> ch(nc + 1);
+    std::vector<uint32_t> cs(nc + 1, 0xA7A7A7A7u);
+    uint8_t* slot = (uint8_t*)malloc(slots ? slots : 1);  // exactly the slots: a write outside them is one outside a heap block
+    if (nc) {
+        P.plan = nullptr; P.chunks = ch.data();
+        kc_launch_s2_range_plan(P, nullptr);
+        KcS2RangeDecodeParams D;
+        memset(&D, 0, sizeof(D));
+        D.src = src; D.chunks = ch.data(); D.n_chunks = nc; D.dst = dst; D.slots = slot; D.ignore_crc = ignore_crc; D.status = cs.data();
+        kc_launch_s2_range_decode(D, nullptr);
+    }
+    free(slot);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t j = live[i];
+        uint32_t v = 0;
+        for (uint32_t k = 0; k < H[i].n_chunks && !v; k++) v = cs[Q[i].chunk0 + k];
+        if (!v) v = H[i].status;
+        status[j] = v;
+        uint64_t g = (v == KCS2D_OK || v == KCS2D_EOF) ? H[i].got : 0;
+        if (g > Q[i].len) g = Q[i].len;
+        got[j] = g;
+        if (g < Q[i].len) memset(dst + out_off[j] + g, 0, (size_t)(Q[i].len - g));
+    }
+    return 0;
 }
 
 int kcemu_s2_decode_blocks_all(const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* bound,

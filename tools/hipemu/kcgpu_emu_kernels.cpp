@@ -20,3 +20,4 @@
 #include "../../compress_amd/csrc/kc_zstd_decode_all.hip"
 #include "../../compress_amd/csrc/kc_s2_plan.hip"
 #include "../../compress_amd/csrc/kc_s2_decode_all.hip"
+#include "../../compress_amd/csrc/kc_s2_ranges.hip"

@@ -10,8 +10,8 @@ struct ZdSym { uint16_t base; uint8_t sym; uint8_t nb; };  // FSE decoding cell:
 
 struct ZdShared {
     uint16_t huf[1 << 11];  // symbol << 8 | nBits, index = next tableLog bits
-    ZdSym ll[1 << 9], of[1 << 8], ml[1 << 9];
-    ZdSym wt[1 << 7];       // FSE table of the Huffman weights
+    ZdSym ll[1 << 9], of[1 << 9], ml[1 << 9];  // the reference reads a table log of up to 9 for all three (zstd/fse_decoder.go tablelogAbsoluteMax)
+    ZdSym wt[1 << 7];       // FSE table of the Huffman weights, up to table log 7 (a larger one goes to the frame's literal scratch)
     uint8_t weights[256];
     int16_t norm[64];
     uint16_t next[64];
@@ -78,6 +78,7 @@ __device__ int zd_read_ncount(const uint8_t* p, int n, int maxSym, int maxLog, i
         if (v < lowThreshold) b.bit += bits - 1;
         else { v = (int)b.take(bits); if (v >= (1 << (bits - 1))) v -= lowThreshold; }
         const int prob = v - 1;
+        if (prob > 32767) return 0;  // (table log 15, one symbol with every cell: no stream can follow such a table)
         norm[sym++] = (int16_t)prob;
         remaining -= prob < 0 ? 1 : prob;
         if (prob == 0) {
@@ -138,7 +139,7 @@ __constant__ uint32_t kMLBase[53] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15
 __device__ int zd_seq_table(int mode, int kind, const uint8_t* p, int n, ZdShared& S) {
     ZdSym* dt = kind == 0 ? S.ll : (kind == 1 ? S.of : S.ml);
     const int maxSym = kind == 0 ? 35 : (kind == 1 ? 30 : 52);  // maxOffsetLengthSymbol = 30 (zstd/fse_predefined.go:45)
-    const int maxLog = kind == 1 ? 8 : 9;
+    const int maxLog = 9;
     if (mode == 0) {
         const int16_t* src = kind == 0 ? kLLNorm : (kind == 1 ? kOFNorm : kMLNorm);
         const int ns = kind == 0 ? 36 : (kind == 1 ? 29 : 53);
@@ -169,12 +170,22 @@ __device__ int zd_seq_table(int mode, int kind, const uint8_t* p, int n, ZdShare
 }
 
 // FSE-compressed Huffman weights (huff0/decompress.go:57-70 -> fse.Decompress).  Lane 0.  Returns count or -1.
-__device__ int zd_fse_weights(const uint8_t* p, int n, ZdShared& S, uint8_t* out) {
+// The reference's fse package takes a table log of up to 15 and any of 256 symbols here (fse/decompress.go readNCount), whatever the
+// weights turn out to be.  The counts live in S.huf, which the new code is about to replace; a table of log 8 or more lives in
+// `scratch` (the frame's literal scratch, free until this block's literals are decoded), and is refused if that cannot hold it.
+__device__ int zd_fse_weights(const uint8_t* p, int n, ZdShared& S, uint8_t* out, uint8_t* scratch, uint32_t scratchBytes) {
     int ns = 0, tl = 0;
-    const int hdr = zd_read_ncount(p, n, 255 > 63 ? 63 : 255, 7, S.norm, &ns, &tl);  // weights are < 16: 64 norm slots are plenty
+    int16_t* norm = (int16_t*)S.huf;
+    uint16_t* next = S.huf + 256;
+    const int hdr = zd_read_ncount(p, n, 255, 15, norm, &ns, &tl);
     if (hdr == 0 || hdr >= n) return -1;
     ZdSym* dt = S.wt;  // the sequence tables must survive: a later block may use them in repeat mode
-    if (!zd_build_fse(S.norm, ns, tl, dt, S.next)) return -1;
+    if (tl > 7) {
+        const uint32_t skip = (uint32_t)(4 - ((uintptr_t)scratch & 3)) & 3;
+        if (scratchBytes < skip || ((size_t)sizeof(ZdSym) << tl) > (size_t)(scratchBytes - skip)) return -1;
+        dt = (ZdSym*)(scratch + skip);
+    }
+    if (!zd_build_fse(norm, ns, tl, dt, next)) return -1;
     ZdRBits br;
     if (!br.init(p + hdr, n - hdr)) return -1;
     uint32_t s1 = br.read(tl), s2 = br.read(tl);

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(64) void kc_zstd_decode_kernel(KcZstdDecParams P) {
                     } else {
                         used = 1 + hb;
                         if (hb == 0 || used > left) e2 = 7;
-                        else { nw = zd_fse_weights(q + 1, hb, S, S.weights); if (nw <= 0) e2 = 7; }
+                        else { nw = zd_fse_weights(q + 1, hb, S, S.weights, lits, (uint32_t)P.lit_stride); if (nw <= 0) e2 = 7; }
                     }
                     int tableLog = 0;
                     if (!e2) {

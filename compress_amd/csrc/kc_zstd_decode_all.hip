@@ -210,7 +210,7 @@ __global__ __launch_bounds__(64) void kc_zstd_decode_all_kernel(KcZdDecodeParams
                     } else {
                         used = 1 + hb;
                         if (hb == 0 || used > left) e2 = 1;
-                        else { nw = zd_fse_weights(q + 1, hb, S, S.weights); if (nw <= 0) e2 = 1; }
+                        else { nw = zd_fse_weights(q + 1, hb, S, S.weights, lits, KC_ZD_LIT_STRIDE); if (nw <= 0) e2 = 1; }
                     }
                     int tableLog = 0;
                     if (!e2) {

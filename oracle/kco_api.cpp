@@ -595,8 +595,9 @@ int64_t kco_zstd_inspect(const uint8_t* enc, uint64_t n, char* out, uint64_t cap
     fd.trace = &tr;
     Bytes content;
     const size_t used = fd.decodeFrame(enc, (size_t)n, nullptr, &content);
-    char tb[192];
-    snprintf(tb, sizeof(tb), "\nframe: consumed=%zu decoded=%zu repeat codes REP1=%zu REP2=%zu REP3=%zu", used, content.size(), fd.repSeen[1], fd.repSeen[2], fd.repSeen[3]);
+    char tb[256];
+    snprintf(tb, sizeof(tb), "\nframe: consumed=%zu decoded=%zu repeat codes REP1=%zu REP2=%zu REP3=%zu offset codes LOW=%zu HIGH=%zu", used, content.size(),
+             fd.repSeen[1], fd.repSeen[2], fd.repSeen[3], fd.ofCodeLow, fd.ofCodeHigh);
     tr += tb;
     if (tr.size() + 1 > cap) return -2;
     memcpy(out, tr.c_str(), tr.size() + 1);

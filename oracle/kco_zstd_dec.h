@@ -120,6 +120,7 @@ struct FrameDec {
     Bytes out;          // regenerated content of the frame
     size_t histBase = 0;  // dictionary bytes logically in front of `out`
     size_t repSeen[4] = {0, 0, 0, 0};  // inspection: sequences carrying repeat-offset code 1 / 2 / 3 in the whole frame
+    size_t ofCodeLow = 0, ofCodeHigh = 0;  // inspection: sequences with an offset code of at most 24 / above 24
     std::string* trace = nullptr;  // inspection (kco_zstd_inspect): one line per block with its modes and first sequences
 
     static uint32_t llBase(int c) { uint32_t b = 0; for (int i = 0; i < c; i++) b += 1u << zfse::llBitsTable[i]; return b; }
@@ -189,7 +190,7 @@ struct FrameDec {
 
     // blockdec.go:560-640: one sequence table according to its compression mode.  Advances *pp.
     bool readSeqTable(int mode, int kind, const uint8_t** pp, const uint8_t* end, SeqTable* t) {
-        static const int maxSym[3] = {35, 30, 52}, maxLog[3] = {9, 8, 9};  // maxOffsetLengthSymbol = 30 (zstd/fse_predefined.go:45)
+        static const int maxSym[3] = {35, 30, 52}, maxLog[3] = {9, 9, 9};  // maxOffsetLengthSymbol = 30 (zstd/fse_predefined.go:45); one limit for all three logs (fse_decoder.go tablelogAbsoluteMax)
         if (mode == 0) {  // predefined
             zfse::Predef& pd = zfse::predef();
             return t->fromNorm(pd.enc[kind].norm, pd.enc[kind].symbolLen, pd.enc[kind].actualTableLog);
@@ -261,6 +262,7 @@ struct FrameDec {
             const uint32_t mlen = mlBase(mc) + (uint32_t)br.read(zfse::mlBitsTable[mc]);
             const uint32_t llen = llBase(lc) + (uint32_t)br.read(zfse::llBitsTable[lc]);
             if (trace && ofVal <= 3) repSeen[ofVal]++;
+            if (trace) (oc <= 24 ? ofCodeLow : ofCodeHigh)++;
             if (trace && i < 4) {
                 char tb[96];
                 snprintf(tb, sizeof(tb), " [ll=%u ml=%u %s%llu]", llen, mlen, ofVal > 3 ? "off=" : "REP", (unsigned long long)(ofVal > 3 ? ofVal - 3 : ofVal));
@@ -275,7 +277,7 @@ struct FrameDec {
                 if (idx == 1) off = rep[0];
                 else {
                     off = idx == 4 ? rep[0] - 1 : rep[idx - 1];
-                    if (off == 0) return false;  // "corrupt: offset 0"
+                    if (off == 0) off = 1;  // "0 is not valid; input is corrupted; force offset to 1" (seqdec_generic.go:75)
                     if (idx != 2) rep[2] = rep[1];
                     rep[1] = rep[0];
                     rep[0] = off;

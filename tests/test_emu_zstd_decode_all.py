@@ -1,14 +1,12 @@
 """The DecodeAll kernels (kc_zstd_plan.hip, kc_zstd_decode_all.hip) on the CPU wave emulator (tools/hipemu/kcemu.cpp:
 kcemu_zstd_decode_all — plan, decode, XXH64, verdict, compaction as one batch) against the reference's decoder fixtures and the
 reference's own DecodeAll (translated: oracle_goref.zstd_decode_all)."""
-import ctypes as C
 import os
 import zipfile
 
-import numpy as np
 import pytest
 
-import emu_lib
+from zstd_frame_cases import emu_decode_all as decode_all
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REFIN = os.path.join(HERE, "golden", "ref_inputs")
@@ -26,31 +24,6 @@ def G():
 def _members(name, suffix=None):
     z = zipfile.ZipFile(os.path.join(REFIN, name))
     return [(m, z.read(m)) for m in z.namelist() if not m.endswith("/") and (suffix is None or m.endswith(suffix))]
-
-
-def decode_all(inputs, cap, dicts=(), max_memory=64 << 30, max_window=1 << 29, ignore_checksum=False):
-    """(list of bytes, status[n]) of kcemu_zstd_decode_all; GUARD bytes around dst are checked."""
-    L = emu_lib.lib()
-    L.kcemu_zstd_decode_all.restype = C.c_int
-    L.kcemu_zstd_decode_all.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32,
-                                        C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-    n = len(inputs)
-    off = np.zeros(n + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(x) for x in inputs])
-    src = np.frombuffer(b"".join(inputs) + b"\0", dtype=np.uint8).copy()
-    doff = np.zeros(len(dicts) + 1, dtype=np.uint64)
-    doff[1:] = np.cumsum([len(d) for d in dicts])
-    dblob = np.frombuffer(b"".join(dicts) + b"\0", dtype=np.uint8).copy()
-    guard = 64
-    dst = np.full(cap + 2 * guard, 0xA5, dtype=np.uint8)
-    out_off = np.zeros(n + 1, dtype=np.uint64)
-    status = np.zeros(n, dtype=np.uint32)
-    r = L.kcemu_zstd_decode_all(src.ctypes.data, off.ctypes.data, n, max_memory, max_window, int(ignore_checksum), dblob.ctypes.data, doff.ctypes.data,
-                                len(dicts), dst.ctypes.data + guard, cap, out_off.ctypes.data, status.ctypes.data)
-    assert r == 0, r
-    assert np.all(dst[:guard] == 0xA5) and np.all(dst[guard + cap:] == 0xA5), "written outside dst"
-    body = dst[guard:guard + cap]
-    return [body[int(out_off[i]):int(out_off[i + 1])].tobytes() for i in range(n)], status
 
 
 def test_good_frames(G):

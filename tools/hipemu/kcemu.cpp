@@ -71,7 +71,16 @@ int kcemu_zstd_decode_all(const uint8_t* src, const uint64_t* in_off, uint32_t n
     for (uint32_t k = 0; k < n_dicts; k++) {
         const uint8_t* content = nullptr;
         uint64_t clen = 0;
-        if (kc_dict_load_decoder(dict_blobs + dict_off[k], dict_off[k + 1] - dict_off[k], &dicts[k], &content, &clen) != 0) return -1;
+        const uint8_t* blob = dict_blobs + dict_off[k];
+        const uint64_t blen = dict_off[k + 1] - dict_off[k];
+        if (blen >= 8 && memcmp(blob, "KCRD", 4) == 0) {  // a raw dictionary (WithDecoderDictRaw): "KCRD", id, content
+            memset(&dicts[k], 0, sizeof(dicts[k]));
+            memcpy(&dicts[k].id, blob + 4, 4);
+            dicts[k].rep[0] = 1; dicts[k].rep[1] = 4; dicts[k].rep[2] = 8;
+            dicts[k].content_len = (uint32_t)(blen - 8);
+            content = blob + 8;
+            clen = blen - 8;
+        } else if (kc_dict_load_decoder(blob, blen, &dicts[k], &content, &clen) != 0) return -1;
         dicts[k].content_off = arena.size();
         arena.insert(arena.end(), content, content + clen);
         arena.resize((arena.size() + 15) & ~(size_t)15);

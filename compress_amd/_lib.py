@@ -50,6 +50,7 @@ SYMBOLS = [
     "kc_last_timings", "kc_corpus_fill", "kc_ctx_set_option", "kc_ctx_get_option", "kc_zstd_encode_jobs", "kc_zstd_job_size", "kc_zstd_overlap_size",
     "kc_zstd_dopts_default", "kc_zstd_dopts_free", "kc_zstd_dopts_max_memory", "kc_zstd_dopts_max_window", "kc_zstd_dopts_ignore_checksum", "kc_zstd_dopts_dict", "kc_zstd_dopts_dict_raw",
     "kc_zstd_decode_all_dev", "kc_zstd_decode_all", "kc_zstd_decode_all_bound_dev", "kc_zstd_decode_all_bound",
+    "kc_zstd_dstream_new", "kc_zstd_dstream_feed", "kc_zstd_dstream_reset", "kc_zstd_dstream_free",
     "kc_s2_ropts_default", "kc_s2_ropts_free", "kc_s2_ropts_max_block_size", "kc_s2_ropts_ignore_crc", "kc_s2_ropts_ignore_stream_identifier",
     "kc_s2_decode_streams_dev", "kc_s2_decode_streams", "kc_s2_decode_streams_bound_dev", "kc_s2_decode_streams_bound",
     "kc_s2_decode_blocks_all_dev", "kc_s2_decode_blocks_all", "kc_s2_decode_blocks_all_bound_dev", "kc_s2_decode_blocks_all_bound",
@@ -69,6 +70,7 @@ OPT_STAGE2_STREAM = 31
 OPT_HOST_CHUNK_MIB_APPEND = 32
 OPT_HOST_ROLL, OPT_HOST_ROLL_MIB = 33, 34
 OPT_S2_HOOK_HOST_FIRST = 35
+OPT_DSTREAM_BLOCKS = 36
 _PATHS = {"auto": PATH_AUTO, "hbm": PATH_HBM, "lds": PATH_LDS, None: PATH_AUTO}
 
 _lib = None
@@ -213,6 +215,14 @@ def load():
         f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp]
         f.restype = C.c_int
     L.kc_s2_decode_blocks_dev.restype = C.c_int
+    L.kc_zstd_dstream_new.argtypes = [vp, vp]
+    L.kc_zstd_dstream_new.restype = vp
+    L.kc_zstd_dstream_feed.argtypes = [vp, vp, u64, C.c_int, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint32)]
+    L.kc_zstd_dstream_feed.restype = C.c_int
+    L.kc_zstd_dstream_reset.argtypes = [vp]
+    L.kc_zstd_dstream_reset.restype = C.c_int
+    L.kc_zstd_dstream_free.argtypes = [vp]
+    L.kc_zstd_dstream_free.restype = None
     L.kc_s2_ropts_default.argtypes = []
     L.kc_s2_ropts_default.restype = vp
     L.kc_s2_ropts_free.argtypes = [vp]

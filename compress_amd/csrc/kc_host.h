@@ -1,7 +1,7 @@
 #pragma once
 // kc_host.h — internal header of the host side of the C ABI (include/kcgpu.h): the context, its scratch buffers and the batch
 // records shared by the translation units kc_ctx.cpp (options, context), kc_batch.cpp (the zstd device pipeline), kc_zstd_host.cpp
-// (host-buffer entry points), kc_jobs.cpp (WithConcurrentBlocks), kc_s2_api.cpp (S2), kc_zstd_dec_api.cpp (DecodeAll), kc_s2_dec_api.cpp (s2.Reader) and kc_hook.cpp
+// (host-buffer entry points), kc_jobs.cpp (WithConcurrentBlocks), kc_s2_api.cpp (S2), kc_zstd_dec_api.cpp (DecodeAll), kc_zstd_dstream_api.cpp (the stream reader), kc_s2_dec_api.cpp (s2.Reader) and kc_hook.cpp
 // (the WriterCustomEncoder hook).
 // Not installed: the boundary is include/kcgpu.h.
 // There is deliberately NO CPU fallback in this library: when the device path cannot serve a
@@ -119,6 +119,7 @@ struct KcCfg {
     int64_t xxh_fin_mode = 1;             // kc_xxh64_fin_kernel: how the payload of raw-only frames is stored (KcXxhFinParams.mode)
     int64_t zfast_prescan = -1;           // SpeedFastest: the no-match pre-scan (kc_zstd_prescan.hip): 0 off, 1 on, -1 when the previous batch did not compress
     int64_t job_prime = 1;                // jobs of a WithConcurrentBlocks stream: tables primed from the overlap prefix on the device (0: on the host)
+    int64_t dstream_blocks = 512;         // zstd stream reader: blocks per launch (1 .. 4096)
     int64_t fuse_raw_xxh = 1;             // frames made of raw blocks only: checksum and payload copy in one pass over the source (kc_xxh64_fin_kernel)
 };
 
@@ -205,6 +206,15 @@ struct kc_s2_ropts {
     uint32_t max_block = (uint32_t)KC_S2_MAX_FRAMED_BLOCK;  // Reader.maxBlock (maxBlockSize)
     int ignore_crc = 0;
     int ignore_id = 0;
+};
+
+// the decoderOptions behind kc_zstd_dopts_* (kc_zstd_dec_api.cpp), read by DecodeAll and by the stream reader (kc_zstd_dstream_api.cpp)
+struct kc_zstd_dopts {
+    uint64_t max_memory = (uint64_t)64 << 30;   // decoderOptions.maxDecodedSize
+    uint64_t max_window = (uint64_t)1 << 29;    // decoderOptions.maxWindowSize (MaxWindowSize)
+    int ignore_checksum = 0;
+    std::vector<KcZdDict> dicts;                // content_off = the dictionary's place in `arena`
+    std::vector<uint8_t> arena;                 // the dictionaries' contents, each 16-byte aligned
 };
 
 namespace kci {

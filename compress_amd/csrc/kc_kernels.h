@@ -289,6 +289,90 @@ struct KcZdDecodeParams {
                                  // hashes every frame's decoded bytes at the even indices
 };
 void kc_launch_zstd_decode_all(const KcZdDecodeParams& P, hipStream_t st);
+// ---- zstd.Decoder as a stream reader (kc_zstd_dstream.hip; host side kc_zdstream_host.h, kc_zstd_dstream_api.cpp) ----
+// A launch is a run of whole blocks of ONE frame.  The entropy kernel gives every compressed block a wave (literals and the raw
+// sequence triples into staging), the execute kernel walks the blocks in order on one wave, the checksum kernel carries XXH64 on.
+#define KC_ZS_OWN 0xFFFFFFFFu       // table source: this block's own description
+#define KC_ZS_CARRIED 0xFFFFFFFEu   // table source: the stream's state (the previous launch, a dictionary's tables, or nothing)
+#define KC_ZS_NO_OFF 0xFFFFFFFFFFFFFFFFull
+enum { KC_ZS_HUF = 0, KC_ZS_LL = 1, KC_ZS_OF = 2, KC_ZS_ML = 3 };
+// One block of a launch as the host walk found it from the fixed-position header bytes.
+struct KcZsBlock {
+    uint64_t pos;                // the block's payload in the launch's input
+    uint32_t size;               // Block_Size
+    uint32_t type;               // 0 raw, 1 RLE, 2 compressed
+    uint32_t parsed;             // compressed: the walk got through the literals header, the sequence count and the modes byte
+    uint32_t ltype, regen, comp, lhdr;  // literals section: type, regenerated size, compressed size, header bytes
+    uint32_t nseq, shdr, modes;  // sequences section: count, bytes of the count, the modes byte (nseq > 0)
+    uint32_t src[4];             // table sources (KC_ZS_HUF ..): KC_ZS_OWN, KC_ZS_CARRIED, or the earlier block of the launch that defined it
+    uint32_t def;                // bit k: the launch's last definer of table k — it writes the table into the next state
+    uint32_t wt_bytes;           // scratch for a Huffman weight table of log 8 .. 15 (0: none needed)
+    uint64_t wt_off;
+    uint64_t lit_off;            // the block's literal slice (Huffman literals only: regen bytes)
+    uint64_t seq_off;            // the block's sequence slice in 32-bit words: nseq litLen, nseq matchLen, nseq ofVal
+};
+// The tables a block may repeat and the repeat offsets: the stream's state between launches.  Double-buffered: the waves of a launch
+// read `cur` while its last definers and the executor write `next`.
+struct KcZsTables {
+    uint16_t huf[1 << 11];
+    KcZdCell ll[1 << 9], of[1 << 9], ml[1 << 9];
+    int32_t huf_log, huf_ok;
+    int32_t log[3], ok[3];       // ll, of, ml
+    uint32_t rep[3];
+    uint32_t pad;
+};
+// XXH64 carried over the launches of a frame
+struct KcZsHash {
+    uint64_t v[4];
+    uint64_t total;
+    uint64_t digest;             // written when the frame's last block was in the launch
+    uint32_t tail_n;
+    uint8_t tail[32];
+};
+struct KcZsEntropyParams {
+    const uint8_t* in;
+    uint64_t in_len;
+    const KcZsBlock* blocks;
+    uint32_t n_blocks;
+    uint64_t window;
+    uint8_t* lits;
+    uint64_t lits_len;
+    uint32_t* seqs;
+    uint64_t seqs_len;           // in words
+    uint8_t* wts;
+    const KcZsTables* cur;
+    KcZsTables* next;
+    uint32_t* status;            // per block
+};
+struct KcZsExecParams {
+    const uint8_t* in;
+    const KcZsBlock* blocks;
+    uint32_t n_blocks;
+    uint64_t window;
+    const uint8_t* lits;
+    const uint32_t* seqs;
+    const uint32_t* estatus;     // the entropy kernel's verdicts
+    uint8_t* hist;               // up to `window` bytes of earlier output, then this launch's
+    uint64_t hist_pos, hist_cap;
+    const uint8_t* dict;         // the dictionary's content in front of the buffer (dict_len 0 once the buffer has slid)
+    uint32_t dict_len;
+    uint32_t def_mask;           // tables some block of the launch writes into `next`; the executor carries the others over
+    const KcZsTables* cur;
+    KcZsTables* next;
+    uint32_t* out_size;          // per block: bytes produced
+    uint32_t* status;            // per block, up to and including the first failing one
+    uint64_t* result;            // [0] bytes produced by the blocks in front of the first failing one, [1] their number
+};
+struct KcZsHashParams {
+    const uint8_t* hist;
+    uint64_t start;              // where the launch's output begins
+    const uint64_t* result;      // [0]: its length
+    KcZsHash* h;
+    int final;
+};
+void kc_launch_zstd_dstream_entropy(const KcZsEntropyParams& P, hipStream_t st);
+void kc_launch_zstd_dstream_execute(const KcZsExecParams& P, hipStream_t st);
+void kc_launch_xxh64_stream(const KcZsHashParams& P, hipStream_t st);
 // ---- s2.Reader / s2.Decode as a product (kc_s2_plan_dev.h, kc_s2_plan.hip, kc_s2_decode_all.hip; host side kc_s2_dec_api.cpp) ----
 // Per-stream / per-chunk status classes (include/kcgpu.h KC_S2D_*)
 enum { KCS2D_OK = 0, KCS2D_CORRUPT = 1, KCS2D_CRC = 2, KCS2D_UNSUPPORTED = 3, KCS2D_SIZE = 4, KCS2D_EOF = 5, KCS2D_UNEXPECTED_EOF = 6 };

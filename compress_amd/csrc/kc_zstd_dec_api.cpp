@@ -9,14 +9,6 @@
 #include "kc_host.h"
 #include "kc_zdec_host.h"
 
-struct kc_zstd_dopts {
-    uint64_t max_memory = (uint64_t)64 << 30;   // decoderOptions.maxDecodedSize
-    uint64_t max_window = (uint64_t)1 << 29;    // decoderOptions.maxWindowSize (MaxWindowSize)
-    int ignore_checksum = 0;
-    std::vector<KcZdDict> dicts;                // content_off = the dictionary's place in `arena`
-    std::vector<uint8_t> arena;                 // the dictionaries' contents, each 16-byte aligned
-};
-
 namespace {
 
 enum { ZD_IN_OFF, ZD_NF, ZD_BOUND, ZD_SLOTB, ZD_EXACT, ZD_STATUS, ZD_FRAME0, ZD_SLOT0, ZD_FRAMES, ZD_STAGE, ZD_LITS, ZD_DICTS, ZD_ARENA,

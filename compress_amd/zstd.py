@@ -9,6 +9,7 @@ zstd/decoder_options.go; the bytes come from the HIP engine behind include/kcgpu
     dec = zstd.NewReader(None)
     plain = dec.DecodeAll(frame, b"")                   # == reference DecodeAll(frame, nil)
     out, out_off, status = dec.DecodeUnits(frames, off) # N independent DecodeAll calls, one batch
+    n = zstd.NewReader(open("big.zst", "rb")).WriteTo(w) # == reference NewReader(r) + WriteTo(w): a stream in bounded memory
 """
 import contextlib
 import ctypes as C
@@ -558,7 +559,8 @@ def NewWriter(w, *opts, **kw):
     return Encoder(*opts, w=w, **kw)
 
 
-# ---- zstd.Decoder: DecodeAll over batches on the device (zstd/decoder.go:319-410, decoder_options.go) ----
+# ---- zstd.Decoder: DecodeAll over batches on the device (zstd/decoder.go:319-410, decoder_options.go) and the stream reader
+# (NewReader(r) / Read / WriteTo, decoder.go:88-312) ----
 class DecodeError(ValueError):
     """DecodeAll refused its input.  `name` is the class of the reference's error: KC_ZD_MAGIC (ErrMagicMismatch), KC_ZD_EOF
     (unexpected EOF), KC_ZD_UNKNOWN_DICT, KC_ZD_WINDOW_EXCEEDED, KC_ZD_SIZE_EXCEEDED, KC_ZD_CRC, KC_ZD_CORRUPT (everything else)."""
@@ -567,6 +569,95 @@ class DecodeError(ValueError):
         self.status = int(status)
         self.name = _lib.ZD_NAMES.get(self.status, str(self.status))
         super().__init__("zstd: DecodeAll: %s" % self.name)
+
+
+class ErrDecoderClosed(ValueError):
+    """zstd.ErrDecoderClosed: Read / WriteTo / Reset after Close."""
+
+    def __init__(self):
+        super().__init__("zstd: decoder used after Close")
+
+
+class ErrDecoderNilInput(NotImplementedError):
+    """zstd.ErrDecoderNilInput: Read / WriteTo on a decoder that has no stream (NewReader(None), Reset(None)): only DecodeAll and
+    its batched forms are served then."""
+
+    def __init__(self):
+        super().__init__("zstd: nil input provided as reader: use DecodeAll / DecodeUnits, or Reset(r) with a stream")
+
+
+class StreamBuffer:
+    """The buffering between an io reader and a stream decoder given as three functions: new() -> handle, feed(handle, src, n, eof,
+    dst, dst_cap, consumed*, produced*, status*) -> kc_status (kc_zstd_dstream_feed's signature behind the handle) and free(handle).
+    It pulls r.read(batch_bytes), keeps the tail the decoder has not consumed, and hands the decoded bytes out in slices."""
+
+    def __init__(self, new, feed, free, r, batch_bytes=32 << 20):
+        self._feed, self._free = feed, free
+        self._h = new()
+        if not self._h:
+            raise MemoryError("zstd stream decoder: new() failed")
+        self._r = r
+        self._batch = max(int(batch_bytes), 1)
+        self._in, self._pos, self._eof = b"", 0, False
+        self._cap = max(self._batch, 128 << 10)  # (no block's bound is above 128 KiB)
+        self._out = C.create_string_buffer(self._cap)
+        self._lo = self._hi = 0
+        self.status = 0     # the class of the stream's error, once everything in front of it has been decoded
+        self.done = False   # the stream has ended cleanly
+
+    def close(self):
+        h, self._h = self._h, None
+        if h:
+            self._free(h)
+
+    def _more(self):
+        """Decodes until there are bytes to hand out; False at the stream's end or at its error."""
+        consumed, produced, status = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        while self._lo == self._hi:
+            if self.status or self.done:
+                return False
+            n = len(self._in) - self._pos
+            src = C.cast(C.c_char_p(self._in), C.c_void_p).value + self._pos if n else None
+            rc = self._feed(self._h, src, n, int(self._eof), C.addressof(self._out), self._cap, C.byref(consumed), C.byref(produced), C.byref(status))
+            if rc != 0:
+                raise _lib.KcError(rc, "zstd stream decoder: feed")
+            self._pos += consumed.value
+            self._lo, self._hi = 0, produced.value
+            self.status = status.value
+            if consumed.value or produced.value or status.value:
+                continue
+            if self._eof:  # nothing left and nothing asked for: the clean end
+                self.done = True
+                return False
+            chunk = self._r.read(self._batch)
+            if chunk:
+                self._in = self._in[self._pos:] + bytes(chunk)
+                self._pos = 0
+            else:
+                self._eof = True
+        return True
+
+    def read_into(self, p):
+        """Fills the writable buffer p; the number of bytes (less than len(p) only at the stream's end or in front of its error)."""
+        mv = memoryview(p).cast("B")
+        n = 0
+        while n < len(mv) and self._more():
+            k = min(len(mv) - n, self._hi - self._lo)
+            mv[n:n + k] = memoryview(self._out)[self._lo:self._lo + k].cast("B")
+            self._lo += k
+            n += k
+        return n
+
+    def write_to(self, w):
+        n = 0
+        while self._more():
+            k = w.write(memoryview(self._out)[self._lo:self._hi])
+            k = self._hi - self._lo if k is None else k
+            if k != self._hi - self._lo:
+                raise IOError("short write")
+            n += k
+            self._lo = self._hi
+        return n
 
 
 def _dopt(name, *args):
@@ -624,9 +715,10 @@ def WithDecoderLowmem(b):
 class Decoder:
     """zstd.Decoder for the stateless form: DecodeAll, and its batched forms DecodeUnits (host buffers) and DecodeAllDevice
     (device-resident).  An input is what DecodeAll takes: any concatenation of frames and skippable frames; no decoded size is
-    needed.  The streaming reader (Read / WriteTo over an io.Reader) is not served by the device path."""
+    needed.  With a reader (NewReader(r), Reset(r)) it is the streaming decoder: Read / WriteTo decode r in bounded memory
+    (kc_zstd_dstream_feed: the frame's blocks on many waves, one launch after the other)."""
 
-    def __init__(self, *opts, device=0, stream=None):
+    def __init__(self, *opts, device=0, stream=None, batch_bytes=32 << 20):
         L = _lib.load()
         self._o = C.c_void_p(L.kc_zstd_dopts_default())
         if not self._o:
@@ -635,6 +727,9 @@ class Decoder:
             op(self)
         self._device, self._stream = device, stream
         self._ctx = None
+        self._batch_bytes = batch_bytes
+        self._sb = None       # the stream in progress (StreamBuffer)
+        self._closed = False
 
     def ctx(self):
         if self._ctx is None:
@@ -708,20 +803,70 @@ class Decoder:
                                                status.ctypes.data))
         return out_off, status[:n]
 
+    def Reset(self, r):
+        """Decoder.Reset (decoder.go:166-234): the next stream to read; None releases the current one (Read then raises
+        ErrDecoderNilInput, DecodeAll goes on working)."""
+        if self._closed:
+            raise ErrDecoderClosed()
+        self._drop_stream()
+        if r is None:
+            return
+        self._sb = self._open(r)
+
+    def _open(self, r):
+        """The stream's buffering on the library's three functions (the CPU tests put the wave emulator's in their place)."""
+        ctx = self.ctx()
+        L = ctx.L
+        return StreamBuffer(lambda: L.kc_zstd_dstream_new(ctx.h, self._o), L.kc_zstd_dstream_feed, L.kc_zstd_dstream_free, r, self._batch_bytes)
+
+    def _drop_stream(self):
+        sb, self._sb = self._sb, None
+        if sb is not None:
+            sb.close()
+
+    def _stream_buffer(self):
+        if self._closed:
+            raise ErrDecoderClosed()
+        if self._sb is None:
+            raise ErrDecoderNilInput()
+        return self._sb
+
     def Read(self, p):
-        raise NotImplementedError("the streaming reader is not served by the device path: use DecodeAll / DecodeUnits")
+        """Decoder.Read (decoder.go:120-159): fills p from the decoded stream and returns the count; 0 at the stream's clean end.
+        Raises DecodeError with the class of the stream's error once every byte in front of it has been returned."""
+        sb = self._stream_buffer()
+        n = sb.read_into(p)
+        if n == 0 and len(p) and sb.status:
+            raise DecodeError(sb.status)
+        return n
 
     def WriteTo(self, w):
-        raise NotImplementedError("the streaming reader is not served by the device path: use DecodeAll / DecodeUnits")
+        """Decoder.WriteTo (decoder.go:284-312): writes the rest of the decoded stream to w and returns the byte count.  An error
+        of the stream is raised after the bytes in front of it were written (DecodeError.written = their count)."""
+        sb = self._stream_buffer()
+        n = sb.write_to(w)
+        if sb.status:
+            e = DecodeError(sb.status)
+            e.written = n
+            raise e
+        return n
+
+    def IOReadCloser(self):
+        """Decoder.IOReadCloser (decoder.go:605-632): read / readinto / write_to / close on the same decoder."""
+        return _ReadCloser(self)
 
     def Close(self):
-        """Decoder.Close: the device context is released (and re-created on the next use)."""
+        """Decoder.Close (decoder.go:579-603): the stream and the device context are released; Read / WriteTo / Reset then raise
+        ErrDecoderClosed.  (DecodeAll and its batched forms keep working: their context comes back with the next use.)"""
+        self._closed = True
+        self._drop_stream()
         c, self._ctx = self._ctx, None
         if c is not None:
             c.close()
 
     def __del__(self):
         try:
+            self._drop_stream()
             self.Close()
             if getattr(self, "_o", None):
                 _lib.load().kc_zstd_dopts_free(self._o)
@@ -730,9 +875,33 @@ class Decoder:
             pass
 
 
+class _ReadCloser:
+    def __init__(self, d):
+        self.d = d
+
+    def read(self, n=-1):
+        if n is None or n < 0:
+            import io
+            w = io.BytesIO()
+            self.d.WriteTo(w)
+            return w.getvalue()
+        p = bytearray(n)
+        return bytes(p[:self.d.Read(p)])
+
+    def readinto(self, p):
+        return self.d.Read(p)
+
+    def write_to(self, w):
+        return self.d.WriteTo(w)
+
+    def close(self):
+        self.d.Close()
+
+
 def NewReader(r, *opts, **kw):
-    """zstd.NewReader(r, opts...) (decoder.go:88).  r must be None: the decoder serves DecodeAll and its batched forms; a stream
-    to read from is the streaming reader, which is not part of the device path."""
+    """zstd.NewReader(r, opts...) (decoder.go:88-118).  With r None the decoder serves DecodeAll and its batched forms (Read raises
+    ErrDecoderNilInput); with a reader it streams: Read / WriteTo.  batch_bytes: how much is pulled from r, and decoded, at a time."""
+    d = Decoder(*opts, **kw)
     if r is not None:
-        raise NotImplementedError("zstd.NewReader over an io.Reader (Read / WriteTo) is not served by the device path: pass None and use DecodeAll")
-    return Decoder(*opts, **kw)
+        d.Reset(r)
+    return d

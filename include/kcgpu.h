@@ -19,6 +19,7 @@
  *   kc_s2_encode_stream_dev     == s2.Writer.EncodeBuffer framing        s2/writer.go:357-451
  *   kc_zstd_decode_units_dev    == N x Decoder.DecodeAll (verifier)       zstd/framedec.go, blockdec.go, seqdec_generic.go
  *   kc_zstd_decode_all[_dev]    == N x (*Decoder).DecodeAll(input, nil)   zstd/decoder.go:319-410 (the decoder as a product)
+ *   kc_zstd_dstream_new / _feed == NewReader(r) + (*Decoder).Read / WriteTo zstd/decoder.go:88-312 (one stream, bounded memory)
  *   kc_s2_decode_blocks_dev     == N x s2.Decode (verifier)              s2/decode.go:58, decode_other.go:22
  *   kc_xxh64_units_dev          == xxhash.Digest over each unit          zstd/internal/xxhash/xxhash.go:27-230
  */
@@ -200,6 +201,7 @@ typedef enum {
     KC_OPT_HOST_ROLL = 33,           /* KC_HOST_ROLL              host-buffer entry points, large inputs: 1 (default) = the device's rolling pipeline (sub-batches of all calls in flight staged, encoded on four lanes and drained in arrival order: consecutive calls overlap), 0 = one chunk-fed device batch per call (round 5) */
     KC_OPT_HOST_ROLL_MIB = 34,       /* KC_HOST_ROLL_MIB          rolling pipeline: sub-batch size (0: a quarter of the call's input — SpeedBetterCompression and S2: half —, 64 MiB .. 1 GiB) */
     KC_OPT_S2_HOOK_HOST_FIRST = 35,  /* KC_S2_HOOK_HOST_FIRST     kc_s2_encode_block: how many callers at a time are left to the host's built-in encoder (they get -1) before the overflow goes to the device: -1 (default) the host's hardware threads, 0 every caller to the device (see kc_s2_encode_block) */
+    KC_OPT_DSTREAM_BLOCKS = 36,      /* (no variable)             zstd stream reader (kc_zstd_dstream_new): blocks per launch, 1 .. 4096 (default 512); at 1 every block is a launch of its own */
     KC_OPT_LAST_PRESCAN_UNITS = 102, /* read-only: units of the last batch the pre-scan settled */
     KC_OPT_LAST_PATH = 100,          /* read-only: KC_PATH_HBM / KC_PATH_LDS the last batch ran on */
     KC_OPT_LAST_BATCHES = 101        /* read-only: device batches the last kc_zstd_encode_units_dev / kc_s2_encode_*_dev call was cut into */
@@ -396,6 +398,33 @@ kc_status kc_zstd_decode_all_bound_dev(kc_ctx* ctx, const kc_zstd_dopts* o, cons
                                        uint64_t* bound, uint32_t* status);
 kc_status kc_zstd_decode_all_bound(kc_ctx* ctx, const kc_zstd_dopts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n,
                                    uint64_t* bound, uint32_t* status);
+/* ---- zstd.NewReader(r): the Decoder as a stream reader (zstd/decoder.go:88-118 NewReader, :120-159 Read, :166-234 Reset,
+ * :284-312 WriteTo, :486-567 nextBlockSync, :649-940 startStreamDecoder) ----
+ * One stream at a time is fed piece by piece from host memory and decoded in bounded memory: the device keeps the frame's last
+ * `window` bytes, the tables and repeat offsets a block may reuse, and the running XXH64.  A frame of many blocks is decoded on many
+ * waves: every compressed block's literals and sequences on a wave of its own, then one wave executes the blocks in order.
+ *
+ * kc_zstd_dstream_new (NewReader / Reset): a fresh stream on `ctx` with a copy of the options; blocks per launch from
+ * KC_OPT_DSTREAM_BLOCKS.  kc_zstd_dstream_reset (Decoder.Reset, decoder.go:166): the same object for a new stream.
+ * kc_zstd_dstream_feed: src[0 .. n) is what the caller holds of the stream from the first byte not yet consumed; eof != 0 says nothing
+ * follows it.  A frame header, a block and a checksum are consumed only when whole, a skippable frame's payload piece by piece
+ * (never buffered): the caller presents src[*consumed .. n) again with more behind it; fewer than 128 KiB + 3 bytes are ever left.
+ * Decoded bytes go to dst[0 .. *produced): as many whole blocks as fit dst_cap by their bound (a raw or RLE block: its size; a
+ * compressed block: min(window, 128 KiB)), at most the launch limit at a time; KC_ERR_DST_TOO_SMALL when dst_cap is below one
+ * block's bound.  *status: 0, or the KC_ZD_* class of the first error — the bytes of every block in front of it are produced first
+ * (all of a frame's bytes in front of KC_ZD_CRC), and the stream stays failed: later calls return the class and nothing else.
+ * eof inside a frame is KC_ZD_EOF; eof between frames, an empty stream included, ends the stream cleanly (decoder.go:493).
+ * Verdicts follow the reference's stream form: a window above WithDecoderMaxWindow or WithDecoderMaxMemory is KC_ZD_SIZE_EXCEEDED
+ * (decoder.go:500, :861-866), WithDecoderMaxMemory never bounds the stream's total, ErrFrameSizeExceeded / ErrFrameSizeMismatch
+ * (decoder.go:529-545, :794-801) are KC_ZD_CORRUPT.  Deviations: a stream frame has no 4 GiB limit; the block that overruns
+ * Frame_Content_Size is not handed out in front of its error; a dictionary's content is out of reach once the frame's history has
+ * slid for the first time (more than window + one launch of output in front of it). */
+typedef struct kc_zstd_dstream kc_zstd_dstream;
+kc_zstd_dstream* kc_zstd_dstream_new(kc_ctx* ctx, const kc_zstd_dopts* o);
+kc_status kc_zstd_dstream_feed(kc_zstd_dstream* s, const uint8_t* src, uint64_t n, int eof, uint8_t* dst, uint64_t dst_cap,
+                               uint64_t* consumed, uint64_t* produced, uint32_t* status);
+kc_status kc_zstd_dstream_reset(kc_zstd_dstream* s);
+void kc_zstd_dstream_free(kc_zstd_dstream* s);
 /* ---- s2.Reader / s2.Decode over N independent inputs (s2/reader.go:249-405, s2/decode.go:58-76) ----
  * The S2 decoder as a product: no decoded length is supplied, CRCs are checked, errors carry the reference's classes; untrusted input
  * is safe (every read is checked against the chunk's end, every write against the chunk's own output range).

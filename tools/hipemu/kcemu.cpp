@@ -18,6 +18,8 @@
 #include "../../compress_amd/csrc/kc_zstd_decode_all.hip"
 #include "../../compress_amd/csrc/kc_dict.cpp"       // (host code: the dictionary loader the decoder options use)
 #include "../../compress_amd/csrc/kc_zdec_host.h"
+#include "../../compress_amd/csrc/kc_zstd_dstream.hip"
+#include "../../compress_amd/csrc/kc_zdstream_host.h"
 #include "../../compress_amd/csrc/kc_s2_plan.hip"
 #include "../../compress_amd/csrc/kc_s2_decode_all.hip"
 #include "../../compress_amd/csrc/kc_s2_ranges.hip"
@@ -56,6 +58,35 @@ static int kcemu_s2_decode(const KcS2PlanParams& P0, int ignore_crc, uint8_t* ds
     }
     return 0;
 }
+
+// The stream reader's device over plain memory: every buffer exactly as large as asked for (a write outside it is one outside a heap
+// block), copies are memcpy, the kernels run on the emulator.
+struct KcemuZsDevice : KcZsDevice {
+    void* buf[B_N] = {nullptr};
+    size_t cap[B_N] = {0};
+    int reserve(int which, size_t bytes, void** p) override {
+        if (cap[which] < bytes) {
+            free(buf[which]);
+            buf[which] = malloc(bytes);
+            cap[which] = bytes;
+            memset(buf[which], 0xA7, bytes);
+        }
+        *p = buf[which];
+        return buf[which] ? 0 : -6;
+    }
+    int h2d(void* d, const void* h, size_t n) override { if (n) memcpy(d, h, n); return 0; }
+    int d2h(void* h, const void* d, size_t n) override { if (n) memcpy(h, d, n); return 0; }
+    int d2d(void* d, const void* s, size_t n) override { if (n) memcpy(d, s, n); return 0; }
+    void entropy(const KcZsEntropyParams& P) override { kc_launch_zstd_dstream_entropy(P, nullptr); }
+    void execute(const KcZsExecParams& P) override { kc_launch_zstd_dstream_execute(P, nullptr); }
+    void hash(const KcZsHashParams& P) override { kc_launch_xxh64_stream(P, nullptr); }
+    int sync() override { return 0; }
+    ~KcemuZsDevice() override { for (void* b : buf) free(b); }
+};
+struct KcemuZsStream {
+    KcemuZsDevice dev;
+    KcZsStream s;
+};
 
 extern "C" {
 
@@ -138,6 +169,43 @@ int kcemu_zstd_decode_all(const uint8_t* src, const uint64_t* in_off, uint32_t n
     kc_launch_compact(stage.data(), soff.data(), csize.data(), ooff.data(), dst, nfr, nullptr);
     return 0;
 }
+
+// zstd.NewReader(r) on the emulator: kc_zstd_dstream_new / _feed / _free of include/kcgpu.h without the context — the state machine of
+// kc_zdstream_host.h over KcemuZsDevice.  blocks: blocks per launch (KC_OPT_DSTREAM_BLOCKS); the dictionaries as kcemu_zstd_decode_all
+// takes them.  Returns null on a dictionary the loader refuses.
+void* kcemu_zstd_dstream_new(uint64_t max_memory, uint64_t max_window, int ignore_checksum, uint32_t blocks, const uint8_t* dict_blobs,
+                             const uint64_t* dict_off, uint32_t n_dicts) {
+    KcemuZsStream* z = new KcemuZsStream();
+    z->s.dev = &z->dev;
+    z->s.o.max_memory = max_memory; z->s.o.max_window = max_window; z->s.o.ignore_checksum = ignore_checksum; z->s.o.blocks = blocks;
+    z->s.o.dicts.resize(n_dicts);
+    z->s.o.arena.assign(16, 0);
+    for (uint32_t k = 0; k < n_dicts; k++) {
+        KcZdDict& D = z->s.o.dicts[k];
+        const uint8_t* content = nullptr;
+        uint64_t clen = 0;
+        const uint8_t* blob = dict_blobs + dict_off[k];
+        const uint64_t blen = dict_off[k + 1] - dict_off[k];
+        if (blen >= 8 && memcmp(blob, "KCRD", 4) == 0) {  // a raw dictionary (WithDecoderDictRaw): "KCRD", id, content
+            memset(&D, 0, sizeof(D));
+            memcpy(&D.id, blob + 4, 4);
+            D.rep[0] = 1; D.rep[1] = 4; D.rep[2] = 8;
+            D.content_len = (uint32_t)(blen - 8);
+            content = blob + 8;
+            clen = blen - 8;
+        } else if (kc_dict_load_decoder(blob, blen, &D, &content, &clen) != 0) { delete z; return nullptr; }
+        D.content_off = z->s.o.arena.size();
+        z->s.o.arena.insert(z->s.o.arena.end(), content, content + clen);
+        z->s.o.arena.resize((z->s.o.arena.size() + 15) & ~(size_t)15);
+    }
+    return z;
+}
+int kcemu_zstd_dstream_feed(void* h, const uint8_t* src, uint64_t n, int eof, uint8_t* dst, uint64_t dst_cap, uint64_t* consumed, uint64_t* produced,
+                            uint32_t* status) {
+    return ((KcemuZsStream*)h)->s.feed(src, n, eof, dst, dst_cap, consumed, produced, status);
+}
+int kcemu_zstd_dstream_reset(void* h) { ((KcemuZsStream*)h)->s.reset(); return 0; }
+void kcemu_zstd_dstream_free(void* h) { delete (KcemuZsStream*)h; }
 
 int kcemu_s2_decode_streams(const uint8_t* src, const uint64_t* in_off, uint32_t n, uint32_t max_block, uint32_t max_buf, int ignore_crc, int ignore_id,
                             uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* bound, uint32_t* status) {

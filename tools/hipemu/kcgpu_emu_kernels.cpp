@@ -18,6 +18,7 @@
 #include "../../compress_amd/csrc/kc_s2_decode.hip"
 #include "../../compress_amd/csrc/kc_zstd_plan.hip"
 #include "../../compress_amd/csrc/kc_zstd_decode_all.hip"
+#include "../../compress_amd/csrc/kc_zstd_dstream.hip"
 #include "../../compress_amd/csrc/kc_s2_plan.hip"
 #include "../../compress_amd/csrc/kc_s2_decode_all.hip"
 #include "../../compress_amd/csrc/kc_s2_ranges.hip"

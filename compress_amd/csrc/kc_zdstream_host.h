@@ -5,7 +5,7 @@
 // framedec.go:65-278 reset, blockdec.go:122-212 the block header) and hands the device runs of whole blocks of one frame.
 //
 // The walk reads only fixed-position bytes of a block — its 3-byte header, the literals header, the sequence count and the modes
-// byte —, sizes the block's literal and sequence slices exactly and names, for each of the four tables, where a block that repeats it
+// byte; the last three by the functions the kernels read them with (kc_zblock_dev.h) —, sizes the block's literal and sequence slices exactly and names, for each of the four tables, where a block that repeats it
 // finds it: the block itself, the earlier block of the launch that last defined it, or the stream's carried state.
 //
 // Verdicts where the stream form differs from DecodeAll's:
@@ -25,6 +25,7 @@
 #include <vector>
 #include "../../include/kcgpu.h"
 #include "kc_kernels.h"
+#include "kc_zblock_dev.h"
 
 // What the state machine needs of a device.  Copies and launches are ordered; sync() waits for all of them.  The source of an h2d
 // and the target of a d2h stay untouched until the next sync().
@@ -121,33 +122,18 @@ struct KcZsStream {
         return (int)pos;
     }
 
-    // ---- the fixed-position bytes of a compressed block (the kernel reads the same and refuses a block the walk read otherwise) ----
+    // ---- the fixed-position bytes of a compressed block, by the functions the kernel reads them with (kc_zblock_dev.h): the kernel
+    // refuses a block whose record says otherwise ----
     void walk_compressed(const uint8_t* b, KcZsBlock& R) const {
-        const uint32_t bn = R.size;
         R.parsed = 0;
-        const uint32_t ltype = b[0] & 3, sf = (b[0] >> 2) & 3;
-        const uint32_t need = ltype < 2 ? ((sf & 1) == 0 ? 1 : (sf == 1 ? 2 : 3)) : (sf < 2 ? 3 : (sf == 2 ? 4 : 5));
-        if (need > bn) return;
-        uint32_t hdr, regen, comp;
-        if (ltype < 2) {
-            if ((sf & 1) == 0) { hdr = 1; regen = b[0] >> 3; }
-            else if (sf == 1) { hdr = 2; regen = (b[0] >> 4) | ((uint32_t)b[1] << 4); }
-            else { hdr = 3; regen = (b[0] >> 4) | ((uint32_t)b[1] << 4) | ((uint32_t)b[2] << 12); }
-            comp = ltype == 0 ? regen : 1;
-        } else if (sf < 2) { const uint32_t v = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16); hdr = 3; regen = (v >> 4) & 0x3FF; comp = (v >> 14) & 0x3FF; }
-        else if (sf == 2) { const uint32_t v = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24); hdr = 4; regen = (v >> 4) & 0x3FFF; comp = (v >> 18) & 0x3FFF; }
-        else { const uint64_t v = (uint64_t)b[0] | ((uint64_t)b[1] << 8) | ((uint64_t)b[2] << 16) | ((uint64_t)b[3] << 24) | ((uint64_t)b[4] << 32); hdr = 5; regen = (uint32_t)((v >> 4) & 0x3FFFF); comp = (uint32_t)((v >> 22) & 0x3FFFF); }
-        if (regen > (128u << 10) || (uint64_t)regen > window || (uint64_t)hdr + comp > bn) return;
-        const uint8_t* sp = b + hdr + comp;
-        uint32_t sn = bn - hdr - comp;
-        if (sn < 1) return;
-        uint32_t nseq = sp[0], sh = 1;
-        if (nseq >= 128) {
-            if (nseq < 255) { if (sn < 2) return; nseq = ((nseq - 128) << 8) + sp[1]; sh = 2; }
-            else { if (sn < 3) return; nseq = sp[1] + ((uint32_t)sp[2] << 8) + 0x7F00; sh = 3; }
-        }
+        ZdLitHdr h;
+        if (zd_lit_header(b, (int)R.size, window, h)) return;
+        const uint8_t* sp = b + h.hdr + h.comp;
+        const int sn = (int)R.size - h.hdr - h.comp;
+        int nseq = 0, sh = 0;
+        if (zd_seq_count(sp, sn, nseq, sh)) return;
         if (nseq > 0 && sn - sh < 1) return;
-        R.ltype = ltype; R.regen = regen; R.comp = comp; R.lhdr = hdr; R.nseq = nseq; R.shdr = sh;
+        R.ltype = (uint32_t)h.ltype; R.regen = h.regen; R.comp = (uint32_t)h.comp; R.lhdr = (uint32_t)h.hdr; R.nseq = (uint32_t)nseq; R.shdr = (uint32_t)sh;
         R.modes = nseq ? sp[sh] : 0;
         R.parsed = 1;
     }
@@ -185,8 +171,7 @@ struct KcZsStream {
                 R.seq_off = seqs;
                 seqs += 3 * (uint64_t)R.nseq;
                 for (int kind = 0; kind < 3; kind++) {
-                    const uint32_t mode = (R.modes >> (6 - 2 * kind)) & 3u;
-                    if (mode == 3) R.src[KC_ZS_LL + kind] = last_def[KC_ZS_LL + kind];
+                    if (zd_seq_mode(R.modes, kind) == 3) R.src[KC_ZS_LL + kind] = last_def[KC_ZS_LL + kind];
                     else { R.src[KC_ZS_LL + kind] = KC_ZS_OWN; last_def[KC_ZS_LL + kind] = i; }
                 }
             }

@@ -1,5 +1,6 @@
 // kc_zexec_dev.h — device code shared by the zstd decoders that execute sequences in groups of 64: DecodeAll (kc_zstd_decode_all.hip)
-// and the stream reader (kc_zstd_dstream.hip): what a frame sees behind it, a block's literals, and the group executor.
+// and the stream reader (kc_zstd_dstream.hip): what a frame sees behind it, a block's literals, and the group executor.  (The block
+// parser in front of it is kc_zdec_dev.h, which the verifier shares; the verifier executes its sequences one after the other.)
 #pragma once
 #include "kc_dev.h"
 #include "kc_kernels.h"
@@ -8,8 +9,7 @@
 
 namespace {
 
-#define ZA_SHORT 32u             // copies up to this many bytes are made by the sequence's own lane, longer ones by the whole wave
-#define ZA_MAX_BLOCK (128u << 10)
+#define ZA_SHORT 32u  // copies up to this many bytes are made by the sequence's own lane, longer ones by the whole wave
 
 // what the frame sees behind it: the dictionary's content (if any) in front of its own output
 struct ZaHist {

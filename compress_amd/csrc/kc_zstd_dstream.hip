@@ -9,6 +9,8 @@
 //     runs sequence by sequence — and executes the sequences in groups of 64 (za_execute_group) into the stream's history buffer;
 //   * kc_xxh64_stream_kernel carries the frame's XXH64 over the bytes the launch produced.
 // ofVal is the offset value before repeat-offset resolution: 1 .. 3 is a repeat code, 4 and up the offset ofVal - 3.
+// The block parser is the one all three decoders share (kc_zdec_dev.h; its literals header and sequence count also run on the host,
+// kc_zblock_dev.h, where the walk sizes the slices); the reader's own is where a repeated table comes from and where the results go.
 // Untrusted input: every read is checked against the block's range, every write against the block's slices / the history buffer;
 // every loop runs to a count read and checked beforehand (nSeq, regen, the block's size, the blocks of the launch).
 #include "kc_dev.h"
@@ -19,146 +21,29 @@
 
 namespace {
 
-// The literals header of a compressed block (blockdec.go:275-345).  Returns 0 or the error class.
-struct ZsLitHdr {
-    int ltype, hdr, comp;
-    uint32_t regen;
-    bool four;
-};
-__device__ __forceinline__ int zs_lit_header(const uint8_t* b, int bn, uint64_t window, ZsLitHdr& h) {
-    h.ltype = b[0] & 3;
-    const int sf = (b[0] >> 2) & 3;
-    const int need = h.ltype < 2 ? ((sf & 1) == 0 ? 1 : (sf == 1 ? 2 : 3)) : (sf < 2 ? 3 : (sf == 2 ? 4 : 5));
-    if (need > bn) return KCZD_CORRUPT;
-    h.four = false;
-    if (h.ltype < 2) {
-        if ((sf & 1) == 0) { h.hdr = 1; h.regen = b[0] >> 3; }
-        else if (sf == 1) { h.hdr = 2; h.regen = (b[0] >> 4) | ((uint32_t)b[1] << 4); }
-        else { h.hdr = 3; h.regen = (b[0] >> 4) | ((uint32_t)b[1] << 4) | ((uint32_t)b[2] << 12); }
-        if (h.regen > ZA_MAX_BLOCK || (uint64_t)h.regen > window) return KCZD_WINDOW;
-        if (h.ltype == 0) { if ((uint64_t)h.hdr + h.regen > (uint64_t)bn) return KCZD_CORRUPT; h.comp = (int)h.regen; }
-        else { if (h.hdr + 1 > bn) return KCZD_CORRUPT; h.comp = 1; }
-        return 0;
-    }
-    if (sf < 2) { const uint32_t v = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16); h.hdr = 3; h.regen = (v >> 4) & 0x3FF; h.comp = (v >> 14) & 0x3FF; h.four = sf == 1; }
-    else if (sf == 2) { const uint32_t v = ld32(b); h.hdr = 4; h.regen = (v >> 4) & 0x3FFF; h.comp = (v >> 18) & 0x3FFF; h.four = true; }
-    else { const uint64_t v = (uint64_t)ld32(b) | ((uint64_t)b[4] << 32); h.hdr = 5; h.regen = (uint32_t)((v >> 4) & 0x3FFFF); h.comp = (int)((v >> 22) & 0x3FFFF); h.four = true; }
-    if (h.regen > ZA_MAX_BLOCK || (uint64_t)h.regen > window) return KCZD_WINDOW;
-    if (h.hdr + h.comp > bn) return KCZD_CORRUPT;
-    return 0;
-}
-
-// Huffman_Tree_Description at q (left bytes) -> S.huf, S.iv[V_HUFLOG] (huff0/decompress.go:29-168): weights on lane 0, table fill on
-// all lanes.  Whole wave.  Returns the bytes the description took, or -1.
-__device__ __forceinline__ int zs_huf_table(const uint8_t* q, int left, ZdShared& S, int lane, uint8_t* scratch, uint32_t scratchBytes) {
-    if (lane == 0) {
-        int e2 = 0, used = 0, nw = 0;
-        const int hb = left > 0 ? q[0] : 0;
-        if (left < 2) e2 = 1;
-        else if (hb >= 128) {
-            nw = hb - 127;
-            used = 1 + (nw + 1) / 2;
-            if (used > left) e2 = 1;
-            else for (int k = 0; k < nw; k++) S.weights[k] = (k & 1) ? (q[1 + (k >> 1)] & 15) : (q[1 + (k >> 1)] >> 4);
-        } else {
-            used = 1 + hb;
-            if (hb == 0 || used > left) e2 = 1;
-            else { nw = zd_fse_weights(q + 1, hb, S, S.weights, scratch, scratchBytes); if (nw <= 0) e2 = 1; }
-        }
-        int tableLog = 0;
-        if (!e2) {
-            uint32_t total = 0, rank1 = 0;
-            for (int k = 0; k < nw; k++) { if (S.weights[k] > 11) e2 = 1; total += (1u << (S.weights[k] & 15)) >> 1; rank1 += S.weights[k] == 1; }
-            if (!e2 && total == 0) e2 = 1;
-            if (!e2) {
-                tableLog = zd_hibit(total) + 1;
-                const uint32_t rest = (1u << tableLog) - total;
-                if (tableLog > 11 || rest == 0 || (rest & (rest - 1)) != 0) e2 = 1;
-                else {
-                    const int lastW = zd_hibit(rest) + 1;
-                    rank1 += lastW == 1;
-                    if (rank1 < 2 || (rank1 & 1)) e2 = 1;  // "min elt size, even check failed"
-                    S.weights[nw++] = (uint8_t)lastW;
-                    for (int k = nw; k < 256; k++) S.weights[k] = 0;
-                }
-            }
-        }
-        S.iv[V_HUFLOG] = tableLog;
-        S.iv[V_ERR] = e2;
-        S.iv[V_NBATCH] = used;
-    }
-    KC_WAVE_SYNC();
-    const int e2 = S.iv[V_ERR], used = S.iv[V_NBATCH], tableLog = S.iv[V_HUFLOG];
-    KC_EMU_SYNC();
-    if (e2) return -1;
-    // start of each symbol's cell range: cells are ordered by (weight asc, symbol asc)
-    for (int s0 = 0; s0 < 256; s0 += 64) {
-        const int sy = s0 + lane;
-        const int w = S.weights[sy];
-        if (w) {
-            uint32_t start = 0;
-            for (int t = 0; t < 256; t++) {
-                const int wt = S.weights[t];
-                if (wt && (wt < w || (wt == w && t < sy))) start += (1u << wt) >> 1;
-            }
-            const uint32_t len = (1u << w) >> 1;
-            const uint16_t e = (uint16_t)((sy << 8) | (tableLog + 1 - w));
-            for (uint32_t k = 0; k < len; k++) S.huf[start + k] = e;
-        }
-    }
-    KC_WAVE_SYNC();
-    return used;
-}
-
-// The sequences header of a compressed block behind its literals section (blockdec.go:505-555): count and its bytes.  0 or the class.
-__device__ __forceinline__ int zs_seq_count(const uint8_t* sp, int sn, int& nSeq, int& sh) {
-    if (sn < 1) return KCZD_CORRUPT;
-    nSeq = sp[0];
-    sh = 1;
-    if (nSeq >= 128) {
-        if (nSeq < 255) { if (sn < 2) return KCZD_CORRUPT; nSeq = ((nSeq - 128) << 8) + sp[1]; sh = 2; }
-        else { if (sn < 3) return KCZD_CORRUPT; nSeq = sp[1] + (sp[2] << 8) + 0x7F00; sh = 3; }
-    }
-    return 0;
-}
-
-// Table `kind` (0 ll, 1 of, 2 ml) as the earlier block R of the launch defined it, rebuilt from that block's bytes.  Lane 0.
-// The descriptions in front of it are read for their length only.  Returns false when the block does not define the table.
+// Table `kind` (0 ll, 1 of, 2 ml) as the earlier block R of the launch defined it, rebuilt from that block's bytes into S (with
+// S.iv[V_LLOK + kind]).  Lane 0.  The descriptions in front of it are read for their length only.  Returns false when the block does
+// not define the table.
 __device__ __forceinline__ bool zs_seq_table_from(const uint8_t* in, uint64_t in_len, const KcZsBlock& R, uint64_t window, int kind, ZdShared& S) {
     if (R.type != 2 || R.pos > in_len || (uint64_t)R.size > in_len - R.pos || R.size < 2 || R.size > ZA_MAX_BLOCK) return false;
     const uint8_t* b = in + R.pos;
     const int bn = (int)R.size;
-    ZsLitHdr h;
-    if (zs_lit_header(b, bn, window, h)) return false;
+    ZdLitHdr h;
+    if (zd_lit_header(b, bn, window, h)) return false;
     const uint8_t* sp = b + h.hdr + h.comp;
     int sn = bn - h.hdr - h.comp, nSeq = 0, sh = 0;
-    if (zs_seq_count(sp, sn, nSeq, sh) || nSeq == 0) return false;
+    if (zd_seq_count(sp, sn, nSeq, sh) || nSeq == 0) return false;
     sp += sh; sn -= sh;
     if (sn < 1) return false;
     const uint8_t modes = sp[0];
     int q2 = 1;
     for (int k = 0; k < kind; k++) {
-        const int mode = (modes >> (6 - 2 * k)) & 3;
-        if (mode == 1) q2 += 1;
-        else if (mode == 2) {
-            int ns = 0, tl = 0;
-            if (sn - q2 < 4) return false;
-            const int used = zd_read_ncount(sp + q2, sn - q2, k == 0 ? 35 : 30, 9, S.norm, &ns, &tl);
-            if (used == 0 || used > sn - q2) return false;
-            q2 += used;
-        }
-        if (q2 > sn) return false;
+        const int used = zd_seq_table_skip(zd_seq_mode(modes, k), k, sp + q2, sn - q2, S);
+        if (used < 0) return false;
+        q2 += used;
     }
-    const int mode = (modes >> (6 - 2 * kind)) & 3;
-    if (mode == 3 || (mode == 2 && sn - q2 < 4)) return false;
-    return zd_seq_table(mode, kind, sp + q2, sn - q2, S) >= 0;
-}
-
-__device__ __forceinline__ void zs_cells_in(ZdSym* dst, const KcZdCell* src, int lane) {
-    for (int k = lane; k < (1 << 9); k += 64) { const KcZdCell a = src[k]; dst[k].base = a.base; dst[k].sym = a.sym; dst[k].nb = a.nb; }
-}
-__device__ __forceinline__ void zs_cells_out(KcZdCell* dst, const ZdSym* src, int lane) {
-    for (int k = lane; k < (1 << 9); k += 64) { KcZdCell a; a.base = src[k].base; a.sym = src[k].sym; a.nb = src[k].nb; dst[k] = a; }
+    const int mode = zd_seq_mode(modes, kind);
+    return mode != 3 && zd_seq_table(mode, kind, sp + q2, sn - q2, S) >= 0;
 }
 
 }  // namespace
@@ -180,13 +65,12 @@ __global__ __launch_bounds__(64) void kc_zstd_dstream_entropy_kernel(KcZsEntropy
         const int bn = (int)R.size;
         uint8_t* wscr = R.wt_bytes ? P.wts + R.wt_off : nullptr;
         // ---- literals section (blockdec.go:275-474) ----
-        ZsLitHdr h;
-        if ((err = zs_lit_header(b, bn, P.window, h)) != 0) break;
+        ZdLitHdr h;
+        if ((err = zd_lit_header(b, bn, P.window, h)) != 0) break;
         // the slices were sized by the host walk from the same bytes: a header it read otherwise is not decoded
         if (!R.parsed || (uint32_t)h.ltype != R.ltype || h.regen != R.regen || (uint32_t)h.comp != R.comp || (uint32_t)h.hdr != R.lhdr) { err = KCZD_CORRUPT; break; }
         if (h.ltype >= 2) {
             if (R.lit_off > P.lits_len || (uint64_t)h.regen > P.lits_len - R.lit_off) { err = KCZD_CORRUPT; break; }
-            uint8_t* __restrict__ lits = P.lits + R.lit_off;
             const uint8_t* q = b + h.hdr;
             int left = h.comp;
             if (h.ltype == 3 && R.src[KC_ZS_HUF] == KC_ZS_CARRIED) {
@@ -203,12 +87,12 @@ __global__ __launch_bounds__(64) void kc_zstd_dstream_entropy_kernel(KcZsEntropy
                     if (j >= bi) { err = KCZD_CORRUPT; break; }
                     const KcZsBlock J = P.blocks[j];
                     if (J.type != 2 || J.pos > P.in_len || (uint64_t)J.size > P.in_len - J.pos || J.size < 2 || J.size > ZA_MAX_BLOCK) { err = KCZD_CORRUPT; break; }
-                    ZsLitHdr hj;
-                    if (zs_lit_header(in + J.pos, (int)J.size, P.window, hj) || hj.ltype != 2) { err = KCZD_CORRUPT; break; }
+                    ZdLitHdr hj;
+                    if (zd_lit_header(in + J.pos, (int)J.size, P.window, hj) || hj.ltype != 2) { err = KCZD_CORRUPT; break; }
                     hq = in + J.pos + hj.hdr;
                     hleft = hj.comp;
                 }
-                const int used = zs_huf_table(hq, hleft, S, lane, wscr, R.wt_bytes);
+                const int used = zd_huf_table(hq, hleft, S, lane, wscr, R.wt_bytes);
                 if (used < 0) { err = KCZD_CORRUPT; break; }
                 if (h.ltype == 2) { q += used; left -= used; }
             }
@@ -216,45 +100,13 @@ __global__ __launch_bounds__(64) void kc_zstd_dstream_entropy_kernel(KcZsEntropy
                 for (int k = lane; k < (1 << 11); k += 64) P.next->huf[k] = S.huf[k];
                 if (lane == 0) { P.next->huf_log = S.iv[V_HUFLOG]; P.next->huf_ok = 1; }
             }
-            // streams: one lane each (decompress.go Decompress1X / Decompress4X)
-            const int hlog = S.iv[V_HUFLOG];
-            int sOff = 0, sLen = left, oOff = 0, oLen = (int)h.regen;  // this lane's stream and where its symbols go
-            int nstreams = 1;
-            if (h.four) {
-                if (left < 10) { err = KCZD_CORRUPT; break; }  // the jump table and a byte per stream (decompress_generic.go:19)
-                const int s1 = q[0] | (q[1] << 8), s2 = q[2] | (q[3] << 8), s3 = q[4] | (q[5] << 8);
-                if (6 + s1 + s2 + s3 > left) { err = KCZD_CORRUPT; break; }
-                const int seg = ((int)h.regen + 3) / 4;
-                if (seg * 3 > (int)h.regen) { err = KCZD_CORRUPT; break; }
-                const int k = lane & 3;
-                sOff = 6 + (k > 0 ? s1 : 0) + (k > 1 ? s2 : 0) + (k > 2 ? s3 : 0);
-                sLen = k == 0 ? s1 : (k == 1 ? s2 : (k == 2 ? s3 : left - sOff));
-                oOff = k * seg;
-                oLen = k < 3 ? seg : (int)h.regen - 3 * seg;
-                nstreams = 4;
-            }
-            int serr = 0;
-            if (lane < nstreams) {
-                ZdRBits br;
-                if (!br.init(q + sOff, sLen)) serr = 1;
-                else {
-                    uint8_t* o = lits + oOff;
-                    for (int i = 0; i < oLen; i++) {
-                        const uint16_t e = S.huf[br.peek(hlog)];
-                        o[i] = (uint8_t)(e >> 8);
-                        br.pos -= (e & 0xFF);
-                    }
-                    if (br.pos != 0) serr = 1;
-                }
-            }
-            if (ballot64(serr != 0)) { err = KCZD_CORRUPT; break; }
-            KC_WAVE_SYNC();
+            if ((err = zd_huf_streams(q, left, h.four, h.regen, S, lane, P.lits + R.lit_off)) != 0) break;
         }
         // ---- sequences section (blockdec.go:505-650) ----
         const uint8_t* sp = b + h.hdr + h.comp;
         int sn = bn - h.hdr - h.comp;
         int nSeq = 0, sh = 0;
-        if ((err = zs_seq_count(sp, sn, nSeq, sh)) != 0) break;
+        if ((err = zd_seq_count(sp, sn, nSeq, sh)) != 0) break;
         sp += sh; sn -= sh;
         if ((uint32_t)nSeq != R.nseq) { err = KCZD_CORRUPT; break; }
         if (nSeq == 0) {
@@ -265,98 +117,35 @@ __global__ __launch_bounds__(64) void kc_zstd_dstream_entropy_kernel(KcZsEntropy
         uint32_t* __restrict__ oLL = P.seqs + R.seq_off;
         uint32_t* __restrict__ oML = oLL + nSeq;
         uint32_t* __restrict__ oOF = oML + nSeq;
-        // the carried tables first (all lanes), then lane 0 reads this block's descriptions and rebuilds what an earlier block defined
+        // Repeat_Mode: the table comes from the carried state (all lanes copy it) or from the earlier block of the launch that defined
+        // it (lane 0 rebuilds it from that block's bytes).  A table that is not there stays unmarked, and the block's own table reader
+        // (zd_seq_tables) refuses the mode.
         const uint32_t srcLL = R.src[KC_ZS_LL], srcOF = R.src[KC_ZS_OF], srcML = R.src[KC_ZS_ML];
-        auto seq_src = [&](int kind) { return kind == 0 ? srcLL : (kind == 1 ? srcOF : srcML); };
-        const uint8_t modes = sn >= 1 ? sp[0] : 0;
-        {
-            int e2 = 0;
-            for (int kind = 0; kind < 3; kind++) {
-                if (sn >= 1 && ((modes >> (6 - 2 * kind)) & 3) == 3 && seq_src(kind) == KC_ZS_CARRIED) {
-                    if (!P.cur->ok[kind]) { e2 = 1; break; }  // Repeat_Mode without a table
-                    zs_cells_in(kind == 0 ? S.ll : (kind == 1 ? S.of : S.ml), kind == 0 ? P.cur->ll : (kind == 1 ? P.cur->of : P.cur->ml), lane);
-                    if (lane == 0) S.iv[V_LLLOG + kind] = P.cur->log[kind];
-                }
-            }
-            KC_WAVE_SYNC();
-            if (e2) { err = KCZD_CORRUPT; break; }
+        for (int kind = 0; kind < 3 && sn >= 1; kind++) {
+            if (zd_seq_mode(sp[0], kind) != 3) continue;
+            const uint32_t j = kind == 0 ? srcLL : (kind == 1 ? srcOF : srcML);
+            if (j == KC_ZS_CARRIED) {
+                if (!P.cur->ok[kind]) continue;
+                zd_cells_in(kind == 0 ? S.ll : (kind == 1 ? S.of : S.ml), kind == 0 ? P.cur->ll : (kind == 1 ? P.cur->of : P.cur->ml), 1 << 9, lane);
+                if (lane == 0) { S.iv[V_LLLOG + kind] = P.cur->log[kind]; S.iv[V_LLOK + kind] = 1; }
+            } else if (lane == 0 && j < bi) zs_seq_table_from(in, P.in_len, P.blocks[j], P.window, kind, S);
         }
-        if (lane == 0) {
-            int e2 = 0;
-            int used = 0;
-            if (sn < 1) e2 = 1;
-            else {
-                if (modes & 3) e2 = 1;
-                int q2 = 1;
-                for (int kind = 0; kind < 3 && !e2; kind++) {
-                    const int mode = (modes >> (6 - 2 * kind)) & 3;
-                    if (mode == 3) {
-                        const uint32_t j = seq_src(kind);
-                        if (j == KC_ZS_CARRIED) continue;
-                        if (j >= bi || !zs_seq_table_from(in, P.in_len, P.blocks[j], P.window, kind, S)) e2 = 1;
-                        continue;
-                    }
-                    if (mode == 2 && sn - q2 < 4) { e2 = 1; break; }  // (the reference's table reader wants four readable bytes, fse_decoder.go:57)
-                    const int r = zd_seq_table(mode, kind, sp + q2, sn - q2, S);
-                    if (r < 0) e2 = 1; else q2 += r;
-                }
-                used = q2;
-            }
-            S.iv[V_ERR] = e2;
-            S.iv[V_NBATCH] = used;
-        }
-        KC_WAVE_SYNC();
         {
-            const int e2 = S.iv[V_ERR], used = S.iv[V_NBATCH];
-            KC_EMU_SYNC();
-            if (e2) { err = KCZD_CORRUPT; break; }
+            const int used = zd_seq_tables(sp, sn, S, lane);
+            if (used < 0) { err = KCZD_CORRUPT; break; }
             sp += used; sn -= used;
         }
-        if ((R.def >> KC_ZS_LL) & 1) { zs_cells_out(P.next->ll, S.ll, lane); if (lane == 0) { P.next->log[0] = S.iv[V_LLLOG]; P.next->ok[0] = 1; } }
-        if ((R.def >> KC_ZS_OF) & 1) { zs_cells_out(P.next->of, S.of, lane); if (lane == 0) { P.next->log[1] = S.iv[V_OFLOG]; P.next->ok[1] = 1; } }
-        if ((R.def >> KC_ZS_ML) & 1) { zs_cells_out(P.next->ml, S.ml, lane); if (lane == 0) { P.next->log[2] = S.iv[V_MLLOG]; P.next->ok[2] = 1; } }
-        // decode 64 sequences on lane 0, then store them with all lanes (seqdec.go:221-434 without the offset history)
-        ZdRBits br;
-        br.p = nullptr; br.pos = 0;
-        uint32_t llS = 0, ofS = 0, mlS = 0;
-        int brErr = 0;
-        if (lane == 0) {
-            if (!br.init(sp, sn)) brErr = KCZD_CORRUPT;
-            else {
-                llS = br.read(S.iv[V_LLLOG]); ofS = br.read(S.iv[V_OFLOG]); mlS = br.read(S.iv[V_MLLOG]);
-                if (br.pos < 0) brErr = KCZD_EOF;  // (the bit reader ran dry: io.ErrUnexpectedEOF)
-            }
-        }
-        brErr = uni(brErr);
-        if (brErr) { err = brErr; break; }
+        if ((R.def >> KC_ZS_LL) & 1) { zd_cells_out(P.next->ll, S.ll, 1 << 9, lane); if (lane == 0) { P.next->log[0] = S.iv[V_LLLOG]; P.next->ok[0] = 1; } }
+        if ((R.def >> KC_ZS_OF) & 1) { zd_cells_out(P.next->of, S.of, 1 << 9, lane); if (lane == 0) { P.next->log[1] = S.iv[V_OFLOG]; P.next->ok[1] = 1; } }
+        if ((R.def >> KC_ZS_ML) & 1) { zd_cells_out(P.next->ml, S.ml, 1 << 9, lane); if (lane == 0) { P.next->log[2] = S.iv[V_MLLOG]; P.next->ok[2] = 1; } }
+        // decode 64 sequences on lane 0, then store them with all lanes: the offset values stay unresolved (the executor's)
+        ZdSeqDec sq;
+        if ((err = zd_seq_open(sq, sp, sn, S, lane)) != 0) break;
         for (int s0 = 0; s0 < nSeq && !err; s0 += 64) {
             const int cnt = nSeq - s0 < 64 ? nSeq - s0 : 64;
-            if (lane == 0) {
-                int e2 = 0;
-                for (int i = 0; i < cnt && !e2; i++) {
-                    const ZdSym cl = S.ll[llS], co = S.of[ofS], cm = S.ml[mlS];
-                    if (cl.sym > 35 || cm.sym > 52 || co.sym > 30) { e2 = KCZD_CORRUPT; break; }
-                    uint32_t ofVal;
-                    if (co.sym <= 24) ofVal = (1u << co.sym) + br.read(co.sym);
-                    else { const uint32_t hi = br.read(co.sym - 16); const uint32_t lo = br.read(16); ofVal = (1u << co.sym) + ((hi << 16) | lo); }
-                    const uint32_t mlen = kMLBase[cm.sym] + br.read(kMLBits[cm.sym]);
-                    const uint32_t llen = kLLBase[cl.sym] + br.read(kLLBits[cl.sym]);
-                    if (s0 + i + 1 < nSeq) {
-                        llS = cl.base + br.read(cl.nb);
-                        mlS = cm.base + br.read(cm.nb);
-                        ofS = co.base + br.read(co.nb);
-                    }
-                    if (br.pos < 0) { e2 = KCZD_EOF; break; }
-                    S.seqLL[i] = llen; S.seqML[i] = mlen; S.seqOF[i] = ofVal;
-                }
-                if (!e2 && s0 + cnt >= nSeq && br.pos != 0) e2 = KCZD_CORRUPT;  // "extra bits on block"
-                S.iv[V_ERR] = e2;
-            }
-            KC_WAVE_SYNC();
-            const int e2 = S.iv[V_ERR];
-            if (!e2 && lane < cnt) { oLL[s0 + lane] = S.seqLL[lane]; oML[s0 + lane] = S.seqML[lane]; oOF[s0 + lane] = S.seqOF[lane]; }
-            KC_EMU_SYNC();
-            if (e2) err = e2;
+            err = zd_seq_group(sq, S, lane, s0, cnt, nSeq, [](uint32_t ofVal, uint32_t, uint32_t& off) { off = ofVal; return true; });
+            if (!err && lane < cnt) { oLL[s0 + lane] = S.seqLL[lane]; oML[s0 + lane] = S.seqML[lane]; oOF[s0 + lane] = S.seqOF[lane]; }
+            KC_EMU_SYNC();  // (lane 0 refills the three arrays for the next group)
         }
     } while (false);
     if (lane == 0) P.status[bi] = (uint32_t)err;
@@ -404,22 +193,10 @@ __global__ __launch_bounds__(64) void kc_zstd_dstream_execute_kernel(KcZsExecPar
                 const int cnt = nSeq - s0 < 64 ? nSeq - s0 : 64;
                 if (lane < cnt) { S.seqLL[lane] = iLL[s0 + lane]; S.seqML[lane] = iML[s0 + lane]; S.seqOF[lane] = iOF[s0 + lane]; }
                 KC_WAVE_SYNC();
-                if (lane == 0) {  // the offset history (seqdec.go:262-300): the one thing here that runs sequence by sequence
+                if (lane == 0) {  // the offset history: the one thing here that runs sequence by sequence
                     for (int i = 0; i < cnt; i++) {
-                        const uint32_t ofVal = S.seqOF[i];
-                        uint32_t off;
-                        if (ofVal > 3) { off = ofVal - 3; rep2 = rep1; rep1 = rep0; rep0 = off; }
-                        else {
-                            const uint32_t idx = ofVal + (S.seqLL[i] == 0 ? 1u : 0u);  // 1: repeat 1, 2: repeat 2, 3: repeat 3, 4: repeat 1 minus one byte
-                            if (idx == 1) off = rep0;
-                            else {
-                                off = idx == 4 ? rep0 - 1 : (idx == 2 ? rep1 : rep2);
-                                if (off == 0) off = 1;  // "0 is not valid; input is corrupted; force offset to 1" (seqdec.go:288-292)
-                                if (idx != 2) rep2 = rep1;
-                                rep1 = rep0;
-                                rep0 = off;
-                            }
-                        }
+                        uint32_t off = zd_rep_offset(S.seqOF[i], S.seqLL[i], rep0, rep1, rep2);
+                        if (off == 0) off = rep0 = 1;  // "0 is not valid; input is corrupted; force offset to 1" (seqdec.go:288-292)
                         S.seqOF[i] = off;
                     }
                 }

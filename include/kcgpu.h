@@ -345,7 +345,10 @@ kc_status kc_s2_decode_blocks_dev(kc_ctx* ctx, const uint8_t* d_enc, const uint6
 /* zstd frame decoder (zstd/framedec.go:65-330, blockdec.go:227-690, seqdec_generic.go) over N units, one frame each, for
  * on-device round-trip verification: unit i decodes to d_dst + dst_off[i] and must produce exactly dst_off[i+1]-dst_off[i]
  * bytes; the frame checksum, if present, is checked against XXH64 of the decoded bytes (status 30 on mismatch).  All block,
- * literal and sequence modes; dictionary frames need kc_zstd_decode_units_dict_dev (status 20 otherwise).  enc_off / dst_off / status are host arrays. */
+ * literal and sequence modes; dictionary frames need kc_zstd_decode_units_dict_dev (status 20 otherwise).  enc_off / dst_off / status are host arrays.
+ * The block parser is the one DecodeAll and the stream reader use, so the verifier refuses what the reference refuses in the four-stream
+ * jump table (ten bytes at least), the weight parity check, an FSE description with fewer than four bytes behind it, the literal size
+ * limits (128 KiB and the window) and a window above 2^29 (status 1); a repeat offset that resolves to 0 stays refused. */
 kc_status kc_zstd_decode_units_dev(kc_ctx* ctx, const uint8_t* d_enc, const uint64_t* enc_off, uint32_t n_units, uint8_t* d_dst,
                                    const uint64_t* dst_off, uint32_t* status);
 /* the same with a dictionary's CONTENT (host pointer) as history in front of every frame: frames written with

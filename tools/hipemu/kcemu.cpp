@@ -14,6 +14,7 @@
 #include <vector>
 #include "../../compress_amd/csrc/kc_s2_best.hip"
 #include "../../compress_amd/csrc/kc_zstd_match_best.hip"
+#include "../../compress_amd/csrc/kc_zstd_decode.hip"
 #include "../../compress_amd/csrc/kc_zstd_plan.hip"
 #include "../../compress_amd/csrc/kc_zstd_decode_all.hip"
 #include "../../compress_amd/csrc/kc_dict.cpp"       // (host code: the dictionary loader the decoder options use)
@@ -167,6 +168,29 @@ int kcemu_zstd_decode_all(const uint8_t* src, const uint64_t* in_off, uint32_t n
         out_off[i + 1] = pos;
     }
     kc_launch_compact(stage.data(), soff.data(), csize.data(), ooff.data(), dst, nfr, nullptr);
+    return 0;
+}
+
+// The verifier over n units on the emulator, one frame each and every frame's decoded length given (dst_off): the decode kernel, XXH64 of
+// the decoded ranges and the checksum verdict — kc_zstd_decode_units_dict_dev's sequence (kc_s2_api.cpp) in plain memory.  dict: a raw
+// dictionary's content in front of every frame, or null.  The literal scratch is a heap block of exactly the size the library gives it.
+int kcemu_zstd_decode_units(const uint8_t* enc, const uint64_t* enc_off, uint32_t n, uint8_t* dst, const uint64_t* dst_off, const uint8_t* dict,
+                            uint64_t dict_len, uint32_t* status) {
+    if (n == 0) return 0;
+    std::vector<uint8_t> lits((size_t)n * KC_ZD_LIT_STRIDE, 0xA7);
+    std::vector<uint32_t> stored(n, 0), has(n, 0);
+    std::vector<uint64_t> hash(n, 0);
+    KcZstdDecParams P;
+    memset(&P, 0, sizeof(P));
+    P.enc = enc; P.enc_off = enc_off; P.dst = dst; P.dst_off = dst_off; P.lits = lits.data(); P.lit_stride = KC_ZD_LIT_STRIDE;
+    P.status = status; P.crc_stored = stored.data(); P.has_crc = has.data(); P.n_units = n;
+    P.dict = dict_len ? dict : nullptr; P.dict_len = (uint32_t)dict_len;
+    kc_launch_zstd_decode(P, nullptr);
+    hipemu::set_group(4);
+    kc_launch_xxh64(dst, dst_off, n, hash.data(), nullptr);
+    hipemu::set_group(64);
+    for (uint32_t i = 0; i < n; i++)
+        if (status[i] == 0 && has[i] && (uint32_t)hash[i] != stored[i]) status[i] = 30;  // checksum mismatch
     return 0;
 }
 

@@ -15,6 +15,7 @@
 #include "kco_dict.h"
 #include "kco_zstd_best.h"
 #include "kco_zstd_dec.h"
+#include <cstdio>
 #include <thread>
 #include <atomic>
 #include <memory>
@@ -611,6 +612,18 @@ int64_t kco_s2_encode_snappy(const uint8_t* src, uint64_t n, uint8_t* dst, uint6
 // test diagnostics: number of late raw fallbacks (blockenc.go:811-817) on non-last blocks that changed the carried offsets since the
 // last reset — the situation the device path's speculation re-run handles
 uint64_t kco_debug_late_raw_pops(int reset) { const uint64_t v = kco::lateRawPops().load(); if (reset) kco::lateRawPops().store(0); return v; }
+// Decision counters (kco_counters.h): writes "name\tcount\n" for every counter into out (NUL-terminated); returns the length
+// needed, or -1 if cap is too small.  reset != 0 clears the counters after reading them.
+int64_t kco_debug_counters(char* out, uint64_t cap, int reset) {
+    uint64_t p = 0;
+    for (int i = 0; i < kco::ctr::COUNT; i++) {
+        const uint64_t v = reset ? kco::ctr::table()[i].exchange(0, std::memory_order_relaxed) : kco::ctr::table()[i].load(std::memory_order_relaxed);
+        const int w = snprintf(out + p, p < cap ? cap - p : 0, "%s\t%llu\n", kco::ctr::names()[i], (unsigned long long)v);
+        if (w < 0 || p + (uint64_t)w >= cap) return -1;
+        p += (uint64_t)w;
+    }
+    return (int64_t)p;
+}
 int64_t kco_s2_encode_snappy_best(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t cap) { return s2::EncodeSnappyBest(dst, cap, src, (size_t)n); }
 int64_t kco_s2_encode_best(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t cap) { return s2::EncodeBest(dst, cap, src, (size_t)n); }
 int64_t kco_s2_encode_snappy_better(const uint8_t* src, uint64_t n, uint8_t* dst, uint64_t cap) { return s2::EncodeSnappyBetter(dst, cap, src, (size_t)n); }

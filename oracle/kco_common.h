@@ -19,6 +19,7 @@
 #include <cstddef>
 #include <vector>
 #include <algorithm>
+#include "kco_counters.h"
 
 namespace kco {
 

@@ -153,6 +153,7 @@ struct Scratch {  // fse/fse.go:46
     }
     // fse/compress.go:557 normalizeCount2
     Err normalizeCount2() {
+        ctr::hit(ctr::FSEB_NC2);
         const int16_t notYetAssigned = -2;
         uint32_t distributed = 0;
         uint32_t total = (uint32_t)remain;
@@ -168,6 +169,7 @@ struct Scratch {  // fse/fse.go:46
         }
         uint32_t toDistribute = (1u << tableLog) - distributed;
         if ((total / toDistribute) > lowOne) {
+            ctr::hit(ctr::FSEB_NC2_SECOND_PASS);
             lowOne = (total * 3) / (toDistribute * 2);
             for (int i = 0; i < (int)symbolLen; i++) {
                 uint32_t cnt = count[i];
@@ -176,6 +178,7 @@ struct Scratch {  // fse/fse.go:46
             toDistribute = (1u << tableLog) - distributed;
         }
         if (distributed == (uint32_t)symbolLen + 1) {
+            ctr::hit(ctr::FSEB_NC2_ALL_SMALL);
             int maxV = 0;
             uint32_t maxC = 0;
             for (int i = 0; i < (int)symbolLen; i++) {
@@ -185,11 +188,13 @@ struct Scratch {  // fse/fse.go:46
             return OK;
         }
         if (total == 0) {
+            ctr::hit(ctr::FSEB_NC2_ROUND_ROBIN);
             for (uint32_t i = 0; toDistribute > 0; i = (i + 1) % (uint32_t)symbolLen) {
                 if (norm[i] > 0) { toDistribute--; norm[i]++; }
             }
             return OK;
         }
+        ctr::hit(ctr::FSEB_NC2_PROPORTIONAL);
         uint64_t vStepLog = 62 - (uint64_t)tableLog;
         uint64_t mid = (uint64_t)(((uint64_t)1 << (vStepLog - 1)) - 1);
         uint64_t rStep = ((((uint64_t)1 << vStepLog) * (uint64_t)toDistribute) + mid) / (uint64_t)total;
@@ -403,7 +408,9 @@ struct Scratch {  // fse/fse.go:46
 };
 
 // fse/compress.go:18 Compress.  Output left in s.Out on OK.
-static inline Err Compress(const uint8_t* in, size_t n, Scratch* s) {
+// *why (optional) tells the two causes of ErrIncompressible apart: 1 = by maxCount (:44), 2 = output no smaller than the input (:74).
+static inline Err Compress(const uint8_t* in, size_t n, Scratch* s, int* why = nullptr) {
+    if (why) *why = 0;
     if (n <= 1) return ErrIncompressible;
     s->prepare(in, n);
     s->Out.clear();
@@ -412,7 +419,7 @@ static inline Err Compress(const uint8_t* in, size_t n, Scratch* s) {
     s->clearCount = true;
     s->maxCount = 0;
     if (maxCount == (int)n) return ErrUseRLE;
-    if (maxCount == 1 || maxCount < (int)(n >> 7)) return ErrIncompressible;
+    if (maxCount == 1 || maxCount < (int)(n >> 7)) { if (why) *why = 1; return ErrIncompressible; }
     s->optimalTableLog();
     Err e = s->normalizeCount();
     if (e != OK) return e;
@@ -422,7 +429,7 @@ static inline Err Compress(const uint8_t* in, size_t n, Scratch* s) {
     if (e != OK) return e;
     e = s->compress(in, n);
     if (e != OK) return e;
-    if (s->Out.size() >= n) return ErrIncompressible;
+    if (s->Out.size() >= n) { if (why) *why = 2; return ErrIncompressible; }
     return OK;
 }
 

@@ -172,6 +172,8 @@ struct Scratch {  // huff0/huff0.go:64
         nodeElt* huffNode = nodes + 1;
         uint8_t largestBits = nNbBits(huffNode[lastNonNull]);
         if (largestBits <= maxNbBits) return largestBits;
+        if (maxNbBits >= 5) ctr::hit(ctr::SMH_MAXNBBITS_5 + (maxNbBits - 5));
+        ctr::hit(ctr::SMH_EXCESS_1 + std::min(largestBits - maxNbBits, 4) - 1);
         int totalCost = 0;
         int baseCost = 1 << (largestBits - maxNbBits);
         uint32_t n = (uint32_t)lastNonNull;
@@ -195,36 +197,43 @@ struct Scratch {  // huff0/huff0.go:64
                 }
             }
             while (totalCost > 0) {
+                ctr::hit(ctr::SMH_COST_POSITIVE);
                 uint8_t nBitsToDecrease = (uint8_t)((uint8_t)highBit((uint32_t)totalCost) + 1);
                 for (; nBitsToDecrease > 1; nBitsToDecrease--) {
                     uint32_t highPos = rankLast[nBitsToDecrease];
                     uint32_t lowPos = rankLast[nBitsToDecrease - 1];
                     if (highPos == noSymbol) continue;
-                    if (lowPos == noSymbol) break;
+                    if (lowPos == noSymbol) { ctr::hit(ctr::SMH_BREAK_LOW_EMPTY); break; }
                     uint32_t highTotal = nCount(huffNode[highPos]);
                     uint32_t lowTotal = 2 * nCount(huffNode[lowPos]);
-                    if (highTotal <= lowTotal) break;
+                    if (highTotal <= lowTotal) { ctr::hit(ctr::SMH_BREAK_HIGH_LE_LOW); break; }
                 }
-                while (nBitsToDecrease <= tableLogMax && rankLast[nBitsToDecrease] == noSymbol) nBitsToDecrease++;
+                while (nBitsToDecrease <= tableLogMax && rankLast[nBitsToDecrease] == noSymbol) { ctr::hit(ctr::SMH_SKIP_EMPTY_RANKS); nBitsToDecrease++; }
                 totalCost -= 1 << (nBitsToDecrease - 1);
-                if (rankLast[nBitsToDecrease - 1] == noSymbol) rankLast[nBitsToDecrease - 1] = rankLast[nBitsToDecrease];
+                if (rankLast[nBitsToDecrease - 1] == noSymbol) { ctr::hit(ctr::SMH_SEED_LOWER_RANK); rankLast[nBitsToDecrease - 1] = rankLast[nBitsToDecrease]; }
                 setNbBits(huffNode[rankLast[nBitsToDecrease]], (uint8_t)(1 + nNbBits(huffNode[rankLast[nBitsToDecrease]])));
                 if (rankLast[nBitsToDecrease] == 0) {
+                    ctr::hit(ctr::SMH_RANK_LAST_IS_0);
                     rankLast[nBitsToDecrease] = noSymbol;
                 } else {
                     rankLast[nBitsToDecrease]--;
-                    if (nNbBits(huffNode[rankLast[nBitsToDecrease]]) != (uint8_t)(maxNbBits - nBitsToDecrease))
+                    if (nNbBits(huffNode[rankLast[nBitsToDecrease]]) != (uint8_t)(maxNbBits - nBitsToDecrease)) {
+                        ctr::hit(ctr::SMH_RANK_EMPTIED);
                         rankLast[nBitsToDecrease] = noSymbol;
+                    }
                 }
             }
             while (totalCost < 0) {
+                ctr::hit(ctr::SMH_COST_NEGATIVE);
                 if (rankLast[1] == noSymbol) {
+                    ctr::hit(ctr::SMH_REPAY_RANK1_UNSET);
                     while (nNbBits(huffNode[n]) == maxNbBits) n--;
                     setNbBits(huffNode[n + 1], (uint8_t)(nNbBits(huffNode[n + 1]) - 1));
                     rankLast[1] = n + 1;
                     totalCost++;
                     continue;
                 }
+                ctr::hit(ctr::SMH_REPAY_RANK1_SET);
                 setNbBits(huffNode[rankLast[1] + 1], (uint8_t)(nNbBits(huffNode[rankLast[1] + 1]) - 1));
                 rankLast[1]++;
                 totalCost++;
@@ -279,6 +288,7 @@ struct Scratch {  // huff0/huff0.go:64
         actualTableLog = setMaxHeight((int)nonNullRank);
         uint8_t maxNbBits = actualTableLog;
         if (maxNbBits > tableLogMax) return ErrInternal;
+        if (maxNbBits >= 1) ctr::hit(ctr::HUF_TABLELOG_1 + (maxNbBits - 1));
 
         uint16_t nbPerRank[tableLogMax + 1];
         uint16_t valPerRank[16];
@@ -318,6 +328,7 @@ struct Scratch {  // huff0/huff0.go:64
             huffWeight[n] = v;
             hist[v]++;
         }
+        if (maxSym < 2) ctr::hit(ctr::HWT_MAXSYM_LT_2);
         if (maxSym >= 2) {
             uint32_t huffMaxCnt = 0;
             uint8_t huffMax = 0;
@@ -329,14 +340,19 @@ struct Scratch {  // huff0/huff0.go:64
             }
             fse.HistogramFinished(huffMax, (int)huffMaxCnt);
             fse.TableLog = maxFSETableLog;
-            fseb::Err err = fseb::Compress(huffWeight, maxSym, &fse);
+            int why = 0;
+            fseb::Err err = fseb::Compress(huffWeight, maxSym, &fse, &why);
+            if (err == fseb::OK) ctr::hit((int)fse.Out.size() < (int)(symbolLen >> 1) ? ctr::HWT_FSE_USED : ctr::HWT_FSE_NOT_SMALLER);
+            else if (err == fseb::ErrUseRLE) ctr::hit(ctr::HWT_FSE_USE_RLE);
+            else if (err == fseb::ErrIncompressible) ctr::hit(why == 2 ? ctr::HWT_FSE_INCOMPRESSIBLE_SIZE : ctr::HWT_FSE_INCOMPRESSIBLE_MAXCOUNT);
             if (err == fseb::OK && (int)fse.Out.size() < (int)(symbolLen >> 1)) {
                 Out.push_back((uint8_t)fse.Out.size());
                 Out.insert(Out.end(), fse.Out.begin(), fse.Out.end());
                 return OK;
             }
         }
-        if (maxSym > (256 - 128)) return ErrIncompressible;
+        if (maxSym > (256 - 128)) { ctr::hit(ctr::HWT_OVER_128_SYMBOLS); return ErrIncompressible; }
+        ctr::hit((maxSym & 1) ? ctr::HWT_RAW_ODD : ctr::HWT_RAW_EVEN);
         Out.push_back((uint8_t)(128 | (maxSym - 1)));
         huffWeight[maxSym] = 0;
         for (uint16_t n = 0; n < (uint16_t)maxSym; n += 2)
@@ -382,7 +398,7 @@ struct Scratch {  // huff0/huff0.go:64
             compress1xDo(&Out, src, toDo);
             src += toDo;
             len -= toDo;
-            if (Out.size() - idx > 65535) return ErrIncompressible;
+            if (Out.size() - idx > 65535) { ctr::hit(ctr::HUF_4X_STREAM_TOO_LONG); return ErrIncompressible; }
             if (i < 3) {
                 size_t length = Out.size() - idx;
                 Out[i * 2 + offsetIdx] = (uint8_t)length;
@@ -399,7 +415,7 @@ static inline Err compress(const uint8_t* in, size_t n, Scratch* s, bool four, b
     *reUsed = false;
     Err perr = s->prepare(n);
     if (perr != OK) return perr;
-    auto compressor = [&](void) -> Err { return four ? s->compress4X(in, n) : s->compress1X(in, n); };
+    auto compressor = [&](void) -> Err { ctr::hit(four ? ctr::HUF_4X : ctr::HUF_1X); return four ? s->compress4X(in, n) : s->compress1X(in, n); };
 
     if (s->Reuse == ReusePolicyNone) s->prevTable.len = 0;
     int maxCount = s->maxCount;
@@ -415,9 +431,10 @@ static inline Err compress(const uint8_t* in, size_t n, Scratch* s, bool four, b
     if (maxCount >= (int)n) {
         if (maxCount > (int)n) return ErrInternal;
         if (n == 1) return ErrIncompressible;
+        ctr::hit(ctr::HUF_USE_RLE);
         return ErrUseRLE;
     }
-    if (maxCount == 1 || maxCount < (int)(n >> 7)) return ErrIncompressible;
+    if (maxCount == 1 || maxCount < (int)(n >> 7)) { ctr::hit(ctr::HUF_INCOMPRESSIBLE_MAXCOUNT); return ErrIncompressible; }
     if (s->Reuse == ReusePolicyMust && !canReuse) return ErrIncompressible;
     if ((s->Reuse == ReusePolicyPrefer || s->Reuse == ReusePolicyMust) && canReuse) {
         CTable keepTable = s->cTable;
@@ -439,6 +456,7 @@ static inline Err compress(const uint8_t* in, size_t n, Scratch* s, bool four, b
         int oldSize = s->prevTable.estimateSize(s->count, s->symbolLen);
         int newSize = s->cTable.estimateSize(s->count, s->symbolLen);
         if (oldSize <= hSize + newSize || hSize + 12 >= wantSize) {
+            ctr::hit(ctr::HUF_REUSE_TAKEN);
             CTable keepTable = s->cTable;
             uint8_t keepTL = s->actualTableLog;
             s->cTable = s->prevTable;
@@ -447,17 +465,18 @@ static inline Err compress(const uint8_t* in, size_t n, Scratch* s, bool four, b
             s->cTable = keepTable;
             s->actualTableLog = keepTL;
             if (err != OK) return err;
-            if ((int)s->Out.size() >= wantSize) return ErrIncompressible;
+            if ((int)s->Out.size() >= wantSize) { ctr::hit(ctr::HUF_REUSE_GE_WANTSIZE); return ErrIncompressible; }
             *reUsed = true;
             return OK;
         }
+        ctr::hit(ctr::HUF_REUSE_POSSIBLE_NEW_TABLE);
     }
     err = s->writeTable(s->cTable);
     if (err != OK) { s->OutTableLen = 0; return err; }
     s->OutTableLen = s->Out.size();
     err = compressor();
     if (err != OK) { s->OutTableLen = 0; return err; }
-    if ((int)s->Out.size() >= wantSize) { s->OutTableLen = 0; return ErrIncompressible; }
+    if ((int)s->Out.size() >= wantSize) { ctr::hit(ctr::HUF_NEW_GE_WANTSIZE); s->OutTableLen = 0; return ErrIncompressible; }
     // Move current table into previous.
     s->prevTable = s->cTable;
     s->prevTableLog = s->actualTableLog;

@@ -144,12 +144,22 @@ struct BlockEnc {  // zstd/blockenc.go:17
         output.insert(output.end(), src, src + n);
     }
 
+    // the 1X / 4X / none choice at its four boundary lengths (in encodeLits, blockenc.go:337, and in encode, :481)
+    static void countLitsChoice(size_t n) {
+        if (n == 16) ctr::hit(ctr::BLK_LITS_16_NONE);
+        else if (n == 17) ctr::hit(ctr::BLK_LITS_17_1X);
+        else if (n == 1023) ctr::hit(ctr::BLK_LITS_1023_1X);
+        else if (n == 1024) ctr::hit(ctr::BLK_LITS_1024_4X);
+    }
+
     // blockenc.go:337 encodeLits; returns false on internal error
     bool encodeLits(const uint8_t* lits, size_t n, bool raw) {
         BlockHeader bh;
         bh.setLast(last);
         bh.setSize((uint32_t)n);
         if (n < 8 || (n < 32 && dictLitEnc == nullptr) || raw) {
+            if (n < 8) ctr::hit(ctr::ENCLITS_LT_8);
+            else if (n < 32 && dictLitEnc == nullptr) ctr::hit(ctr::ENCLITS_LT_32_NO_DICT);
             bh.setType(blockTypeRaw);
             bh.appendTo(&output);
             output.insert(output.end(), lits, lits + n);
@@ -162,6 +172,7 @@ struct BlockEnc {  // zstd/blockenc.go:17
             litEnc->Reuse = huff0::ReusePolicyAllow;
             dictLitEnc = nullptr;
         }
+        countLitsChoice(n);
         if (n >= 1024) {
             err = huff0::compress(lits, n, litEnc, true, &reUsed);
         } else if (n > 16) {
@@ -174,7 +185,7 @@ struct BlockEnc {  // zstd/blockenc.go:17
         if (err == huff0::OK && out.size() + 5 > n) {
             LiteralsHeader lh;
             lh.setSizes((int)out.size(), (int)n, single);
-            if (out.size() + (size_t)lh.size() >= n) err = huff0::ErrIncompressible;
+            if (out.size() + (size_t)lh.size() >= n) { ctr::hit(ctr::ENCLITS_NOT_SMALLER); err = huff0::ErrIncompressible; }
         }
         switch (err) {
         case huff0::ErrIncompressible:
@@ -196,6 +207,7 @@ struct BlockEnc {  // zstd/blockenc.go:17
         if (reUsed) lh.setType(literalsBlockTreeless);
         else lh.setType(literalsBlockCompressed);
         lh.setSizes((int)out.size(), (int)n, single);
+        ctr::hit(ctr::LH_COMP_3 + (lh.size() - 3));
         bh.setSize((uint32_t)(out.size() + (size_t)lh.size() + 1));
         bh.appendTo(&output);
         lh.appendTo(&output);
@@ -234,6 +246,12 @@ struct BlockEnc {  // zstd/blockenc.go:17
             s->mlCode = v; mlH[v]++; if (v > mlMax) mlMax = v;
         }
         auto maxOf = [](const uint32_t* h, int n) { uint32_t m = 0; for (int i = 0; i < n; i++) if (h[i] > m) m = h[i]; return (int)m; };
+        ctr::hit(llMax < 16 ? ctr::GC_LL_MAX_LT_16 : llMax < 25 ? ctr::GC_LL_MAX_16_24 : ctr::GC_LL_MAX_GE_25);
+        if (llMax == zfse::maxLiteralLengthSymbol) ctr::hit(ctr::GC_LL_MAX_TOP);
+        ctr::hit(mlMax < 32 ? ctr::GC_ML_MAX_LT_32 : mlMax < 43 ? ctr::GC_ML_MAX_32_42 : ctr::GC_ML_MAX_GE_43);
+        if (mlMax == zfse::maxMatchLengthSymbol) ctr::hit(ctr::GC_ML_MAX_TOP);
+        ctr::hit(ofMax < 8 ? ctr::GC_OF_MAX_LT_8 : ofMax < 16 ? ctr::GC_OF_MAX_8_15 : ctr::GC_OF_MAX_GE_16);
+        if (ofMax == zfse::maxOffsetLengthSymbol) ctr::hit(ctr::GC_OF_MAX_TOP);
         coders.mlEnc->HistogramFinished(mlMax, maxOf(mlH, mlMax + 1));
         coders.ofEnc->HistogramFinished(ofMax, maxOf(ofH, ofMax + 1));
         coders.llEnc->HistogramFinished(llMax, maxOf(llH, llMax + 1));
@@ -247,12 +265,14 @@ struct BlockEnc {  // zstd/blockenc.go:17
         if (sequences.size() == 1 && orgLen > 0 && literals.size() <= 1) {
             Seq seq = sequences[0];
             if (seq.litLen == (uint32_t)literals.size() && seq.offset - 3 == 1) {
+                ctr::hit(ctr::ENCODE_SINGLE_SEQ_RLE);
                 encodeRLE(org[0], sequences[0].matchLen + zstdMinMatch + seq.litLen);
                 return 0;
             }
         }
         int saved = size - (int)literals.size() - (size >> 6);
         if (saved < 16) {
+            ctr::hit(ctr::ENCODE_SAVED_LT_16);
             if (org == nullptr) return 1;
             popOffsets();
             return encodeLits(org, orgLen, rawAllLits) ? 0 : -1;
@@ -271,6 +291,7 @@ struct BlockEnc {  // zstd/blockenc.go:17
             litEnc->Reuse = huff0::ReusePolicyAllow;
             dictLitEnc = nullptr;
         }
+        if (!raw) countLitsChoice(literals.size());
         if (literals.size() >= 1024 && !raw) {
             err = huff0::compress(literals.data(), literals.size(), litEnc, true, &reUsed);
         } else if (literals.size() > 16 && !raw) {
@@ -286,18 +307,20 @@ struct BlockEnc {  // zstd/blockenc.go:17
             int szRaw = lh2.size();
             lh2.setSizes((int)out.size(), (int)literals.size(), single);
             int szComp = lh2.size();
-            if (out.size() + (size_t)szComp >= literals.size() + (size_t)szRaw) err = huff0::ErrIncompressible;
+            if (out.size() + (size_t)szComp >= literals.size() + (size_t)szRaw) { ctr::hit(ctr::ENCODE_NOT_SMALLER); err = huff0::ErrIncompressible; }
         }
         switch (err) {
         case huff0::ErrIncompressible:
             lh.setType(literalsBlockRaw);
             lh.setSize((int)literals.size());
+            ctr::hit(ctr::LH_RAW_1 + (lh.size() - 1));
             lh.appendTo(&output);
             output.insert(output.end(), literals.begin(), literals.end());
             break;
         case huff0::ErrUseRLE:
             lh.setType(literalsBlockRLE);
             lh.setSize((int)literals.size());
+            ctr::hit(ctr::LH_RLE_1 + (lh.size() - 1));
             lh.appendTo(&output);
             output.push_back(literals[0]);
             break;
@@ -305,6 +328,7 @@ struct BlockEnc {  // zstd/blockenc.go:17
             if (reUsed) lh.setType(literalsBlockTreeless);
             else lh.setType(literalsBlockCompressed);
             lh.setSizes((int)out.size(), (int)literals.size(), single);
+            ctr::hit(ctr::LH_COMP_3 + (lh.size() - 3));
             lh.appendTo(&output);
             output.insert(output.end(), out.begin(), out.end());
             litEnc->Reuse = huff0::ReusePolicyAllow;
@@ -313,6 +337,8 @@ struct BlockEnc {  // zstd/blockenc.go:17
         }
         // Sequence compression (:599)
         size_t nSeq = sequences.size();
+        if (nSeq == 127) ctr::hit(ctr::GC_NSEQ_127);
+        else if (nSeq == 128) ctr::hit(ctr::GC_NSEQ_128);
         if (nSeq < 128) {
             output.push_back((uint8_t)nSeq);
         } else if (nSeq < 0x7f00) {
@@ -328,9 +354,9 @@ struct BlockEnc {  // zstd/blockenc.go:17
         FseEncoder* llEnc = coders.llEnc;
         FseEncoder* ofEnc = coders.ofEnc;
         FseEncoder* mlEnc = coders.mlEnc;
-        if (!llEnc->normalizeCount((int)nSeq)) return -1;
-        if (!ofEnc->normalizeCount((int)nSeq)) return -1;
-        if (!mlEnc->normalizeCount((int)nSeq)) return -1;
+        if (!llEnc->normalizeCount((int)nSeq, ctr::LL)) return -1;
+        if (!ofEnc->normalizeCount((int)nSeq, ctr::OF)) return -1;
+        if (!mlEnc->normalizeCount((int)nSeq, ctr::ML)) return -1;
 
         // :633 chooseComp
         auto chooseComp = [](FseEncoder* cur, FseEncoder* prev, FseEncoder* preDef, SeqCompMode* m) -> FseEncoder* {
@@ -371,9 +397,9 @@ struct BlockEnc {  // zstd/blockenc.go:17
             mode |= (uint8_t)(m << 2);
         }
         output.push_back(mode);
-        if (!llEnc->writeCount(&output)) return -1;
-        if (!ofEnc->writeCount(&output)) return -1;
-        if (!mlEnc->writeCount(&output)) return -1;
+        if (!llEnc->writeCount(&output, ctr::LL)) return -1;
+        if (!ofEnc->writeCount(&output, ctr::OF)) return -1;
+        if (!mlEnc->writeCount(&output, ctr::ML)) return -1;
 
         // :725 bitstream
         wr.reset(&output);

@@ -218,12 +218,13 @@ struct FseEncoder {  // zstd/fse_encoder.go:23
         actualTableLog = tableLog;
     }
 
-    // fse_encoder.go:259 normalizeCount; returns false on error
-    bool normalizeCount(int length) {
+    // fse_encoder.go:259 normalizeCount; returns false on error.  `coder` (ctr::LL / OF / ML) only selects the decision counters.
+    bool normalizeCount(int length, int coder = ctr::NONE) {
         static const uint32_t rtbTable[8] = {0, 473195, 504333, 520860, 550000, 700000, 750000, 830000};
         if (reUsed) return true;
         optimalTableLog(length);
         uint8_t tableLog = actualTableLog;
+        ctr::hitc(coder, ctr::TABLELOG_5 + (tableLog - 5));
         uint64_t scale = 62 - (uint64_t)tableLog;
         uint64_t step = ((uint64_t)1 << 62) / (uint64_t)length;
         uint64_t vStep = (uint64_t)1 << (scale - 20);
@@ -231,12 +232,13 @@ struct FseEncoder {  // zstd/fse_encoder.go:23
         int largest = 0;
         int16_t largestP = 0;
         uint32_t lowThreshold = (uint32_t)(length >> tableLog);
-        if (maxCount == length) { useRLE = true; return true; }
+        if (maxCount == length) { ctr::hitc(coder, ctr::USE_RLE); useRLE = true; return true; }
         useRLE = false;
         for (int i = 0; i < (int)symbolLen; i++) {
             uint32_t cnt = count[i];
             if (cnt == 0) { norm[i] = 0; continue; }
             if (cnt <= lowThreshold) {
+                ctr::hitc(coder, ctr::LOWPROB);
                 norm[i] = -1;
                 stillToDistribute--;
             } else {
@@ -244,7 +246,7 @@ struct FseEncoder {  // zstd/fse_encoder.go:23
                 if (proba < 8) {
                     uint64_t restToBeat = vStep * (uint64_t)rtbTable[proba];
                     uint64_t v = (uint64_t)cnt * step - ((uint64_t)proba << scale);
-                    if (v > restToBeat) proba++;
+                    if (v > restToBeat) { ctr::hitc(coder, ctr::ROUND_UP); proba++; }
                 }
                 if (proba > largestP) { largestP = proba; largest = i; }
                 norm[i] = proba;
@@ -252,7 +254,7 @@ struct FseEncoder {  // zstd/fse_encoder.go:23
             }
         }
         if ((int16_t)(-stillToDistribute) >= (norm[largest] >> 1)) {
-            if (!normalizeCount2(length)) return false;
+            if (!normalizeCount2(length, coder)) return false;
             return buildCTable();
         }
         norm[largest] = (int16_t)(norm[largest] + stillToDistribute);
@@ -260,7 +262,8 @@ struct FseEncoder {  // zstd/fse_encoder.go:23
     }
 
     // fse_encoder.go:334 normalizeCount2
-    bool normalizeCount2(int length) {
+    bool normalizeCount2(int length, int coder = ctr::NONE) {
+        ctr::hitc(coder, ctr::NC2);
         const int16_t notYetAssigned = -2;
         uint32_t distributed = 0;
         uint32_t total = (uint32_t)length;
@@ -276,6 +279,7 @@ struct FseEncoder {  // zstd/fse_encoder.go:23
         }
         uint32_t toDistribute = (1u << tableLog) - distributed;
         if ((total / toDistribute) > lowOne) {
+            ctr::hitc(coder, ctr::NC2_SECOND_PASS);
             lowOne = (total * 3) / (toDistribute * 2);
             for (int i = 0; i < (int)symbolLen; i++) {
                 uint32_t cnt = count[i];
@@ -284,6 +288,7 @@ struct FseEncoder {  // zstd/fse_encoder.go:23
             toDistribute = (1u << tableLog) - distributed;
         }
         if (distributed == (uint32_t)symbolLen + 1) {
+            ctr::hitc(coder, ctr::NC2_ALL_SMALL);
             int maxV = 0;
             uint32_t maxC = 0;
             for (int i = 0; i < (int)symbolLen; i++)
@@ -292,11 +297,13 @@ struct FseEncoder {  // zstd/fse_encoder.go:23
             return true;
         }
         if (total == 0) {
+            ctr::hitc(coder, ctr::NC2_ROUND_ROBIN);
             for (uint32_t i = 0; toDistribute > 0; i = (i + 1) % (uint32_t)symbolLen) {
                 if (norm[i] > 0) { toDistribute--; norm[i]++; }
             }
             return true;
         }
+        ctr::hitc(coder, ctr::NC2_PROPORTIONAL);
         uint64_t vStepLog = 62 - (uint64_t)tableLog;
         uint64_t mid = (uint64_t)(((uint64_t)1 << (vStepLog - 1)) - 1);
         uint64_t rStep = ((((uint64_t)1 << vStepLog) * (uint64_t)toDistribute) + mid) / (uint64_t)total;
@@ -316,7 +323,7 @@ struct FseEncoder {  // zstd/fse_encoder.go:23
     }
 
     // fse_encoder.go:488 writeCount — appends to out; returns false on error
-    bool writeCount(Bytes* outv) {
+    bool writeCount(Bytes* outv, int coder = ctr::NONE) {
         if (useRLE) { outv->push_back(rleVal); return true; }
         if (preDefined || reUsed) return true;
         uint8_t tableLog = actualTableLog;
@@ -337,6 +344,7 @@ struct FseEncoder {  // zstd/fse_encoder.go:23
             if (previous0) {
                 uint16_t start = charnum;
                 while (norm[charnum] == 0) charnum++;
+                if (charnum >= start + 24) ctr::hitc(coder, ctr::WC_ZERO_RUN_24);
                 while (charnum >= start + 24) {
                     start += 24;
                     bitStream += (uint32_t)0xFFFF << bitCount;
@@ -345,6 +353,7 @@ struct FseEncoder {  // zstd/fse_encoder.go:23
                     outP += 2;
                     bitStream >>= 16;
                 }
+                if (charnum >= start + 3) ctr::hitc(coder, ctr::WC_ZERO_RUN_3);  // (what the 24-loop left: the loop below is entered)
                 while (charnum >= start + 3) {
                     start += 3;
                     bitStream += (uint32_t)3 << bitCount;
@@ -366,12 +375,13 @@ struct FseEncoder {  // zstd/fse_encoder.go:23
             if (cnt < 0) remaining = (int16_t)(remaining + cnt);
             else remaining = (int16_t)(remaining - cnt);
             cnt++;
-            if (cnt >= threshold) cnt = (int16_t)(cnt + max);
+            if (cnt >= threshold) { ctr::hitc(coder, ctr::WC_CNT_GE_THRESHOLD); cnt = (int16_t)(cnt + max); }
             bitStream += (uint32_t)(int32_t)cnt << bitCount;
             bitCount += nbBits;
             if (cnt < max) bitCount--;
             previous0 = cnt == 1;
             if (remaining < 1) return false;
+            if (remaining < (threshold >> 1)) ctr::hitc(coder, ctr::WC_SHRINK_TWICE);
             while (remaining < threshold) { nbBits--; threshold >>= 1; }
             if (bitCount > 16) {
                 out[outP] = (uint8_t)bitStream;

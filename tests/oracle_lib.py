@@ -170,6 +170,18 @@ class ZstdOracle:
         return buf.raw[:r]
 
 
+def counters(reset=False):
+    """The oracle's decision counters (oracle/kco_counters.h) as {name: hits}, process-wide; reset=True clears them after the read."""
+    L = lib()
+    L.kco_debug_counters.restype = C.c_int64
+    L.kco_debug_counters.argtypes = [C.c_char_p, C.c_uint64, C.c_int]
+    buf = C.create_string_buffer(1 << 16)
+    r = L.kco_debug_counters(buf, len(buf), int(reset))
+    if r < 0:
+        raise RuntimeError("oracle counters: buffer too small")
+    return {k: int(v) for k, v in (ln.split("\t") for ln in buf.value.decode().splitlines())}
+
+
 def zstd_encode_units(src, unit_off, threads=1, **kw):
     """src: bytes/numpy u8; unit_off: numpy u64 [n+1]. Returns (bytes, out_off numpy)."""
     import numpy as np

@@ -12,7 +12,7 @@ ZD_NAMES = {0: "KC_ZD_OK", 1: "KC_ZD_MAGIC", 2: "KC_ZD_EOF", 3: "KC_ZD_UNKNOWN_D
             6: "KC_ZD_CRC", 7: "KC_ZD_CORRUPT"}
 # per-input status classes of s2.Reader / s2.Decode (include/kcgpu.h KC_S2D_*)
 S2D_NAMES = {0: "KC_S2D_OK", 1: "KC_S2D_CORRUPT", 2: "KC_S2D_CRC", 3: "KC_S2D_UNSUPPORTED", 4: "KC_S2D_SIZE_EXCEEDED", 5: "KC_S2D_EOF",
-             6: "KC_S2D_UNEXPECTED_EOF"}
+             6: "KC_S2D_UNEXPECTED_EOF", 7: "KC_S2D_CALLBACK"}
 KC_ERR_BAD_ARG, KC_ERR_DST_TOO_SMALL, KC_ERR_HIP, KC_ERR_UNSUPPORTED, KC_ERR_NO_DEVICE, KC_ERR_INTERNAL = -1, -2, -3, -4, -5, -6
 _NAMES = {0: "KC_OK", -1: "KC_ERR_BAD_ARG", -2: "KC_ERR_DST_TOO_SMALL", -3: "KC_ERR_HIP", -4: "KC_ERR_UNSUPPORTED",
           -5: "KC_ERR_NO_DEVICE", -6: "KC_ERR_INTERNAL"}
@@ -57,6 +57,8 @@ SYMBOLS = [
     "kc_s2_index_new", "kc_s2_index_free", "kc_s2_index_load", "kc_s2_index_load_stream", "kc_s2_index_find", "kc_s2_index_total_uncompressed",
     "kc_s2_index_total_compressed", "kc_s2_index_est_block_uncompressed", "kc_s2_index_entries", "kc_s2_index_stream",
     "kc_s2_read_ranges_dev", "kc_s2_read_ranges",
+    "kc_s2_rstream_new", "kc_s2_rstream_feed", "kc_s2_rstream_skip", "kc_s2_rstream_skip_left", "kc_s2_rstream_on_skippable", "kc_s2_rstream_reset",
+    "kc_s2_rstream_free",
     "kc_probe_table_pattern", "kc_probe_pcie", "kc_ctx_trim", "kc_device_trim", "kc_s2_hook_declined", "kc_create_error", "kc_host_alloc", "kc_host_free",
 ]
 
@@ -71,6 +73,9 @@ OPT_HOST_CHUNK_MIB_APPEND = 32
 OPT_HOST_ROLL, OPT_HOST_ROLL_MIB = 33, 34
 OPT_S2_HOOK_HOST_FIRST = 35
 OPT_DSTREAM_BLOCKS = 36
+OPT_S2_RSTREAM_CHUNKS = 37
+# kc_s2_skippable_fn: int fn(void* user, uint8_t id, const uint8_t* piece, uint64_t n, uint64_t left)
+S2_SKIPPABLE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint8, C.POINTER(C.c_uint8), C.c_uint64, C.c_uint64)
 _PATHS = {"auto": PATH_AUTO, "hbm": PATH_HBM, "lds": PATH_LDS, None: PATH_AUTO}
 
 _lib = None
@@ -254,6 +259,20 @@ def load():
         f = getattr(L, n)
         f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, u64, vp, vp, vp]
         f.restype = C.c_int
+    L.kc_s2_rstream_new.argtypes = [vp, vp]
+    L.kc_s2_rstream_new.restype = vp
+    L.kc_s2_rstream_feed.argtypes = [vp, vp, u64, C.c_int, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_uint32)]
+    L.kc_s2_rstream_feed.restype = C.c_int
+    L.kc_s2_rstream_skip.argtypes = [vp, u64]
+    L.kc_s2_rstream_skip.restype = C.c_int
+    L.kc_s2_rstream_skip_left.argtypes = [vp]
+    L.kc_s2_rstream_skip_left.restype = u64
+    L.kc_s2_rstream_on_skippable.argtypes = [vp, C.c_uint8, S2_SKIPPABLE_FN, vp]
+    L.kc_s2_rstream_on_skippable.restype = C.c_int
+    L.kc_s2_rstream_reset.argtypes = [vp]
+    L.kc_s2_rstream_reset.restype = C.c_int
+    L.kc_s2_rstream_free.argtypes = [vp]
+    L.kc_s2_rstream_free.restype = None
     L.kc_s2_encode_block.argtypes = [vp, vp, u64, vp, u64]
     L.kc_s2_encode_block.restype = C.c_int64
     L.kc_s2_hook_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]

@@ -244,6 +244,7 @@ kc_status kc_ctx_set_option(kc_ctx* c, int key, int64_t v) {
         case KC_OPT_XXH_FIN_MODE: if (v < 0 || v > 3) return KC_ERR_BAD_ARG; g.xxh_fin_mode = v; break;
         case KC_OPT_JOB_PRIME: g.job_prime = v != 0; break;
         case KC_OPT_DSTREAM_BLOCKS: if (v < 1 || v > 4096) return KC_ERR_BAD_ARG; g.dstream_blocks = v; break;
+        case KC_OPT_S2_RSTREAM_CHUNKS: if (v < 1 || v > 4096) return KC_ERR_BAD_ARG; g.s2_rstream_chunks = v; break;
         case KC_OPT_STAGE2_STREAM: if (c->pend) return KC_ERR_BAD_ARG; c->stream2 = (hipStream_t)(intptr_t)v; break;
         default: return KC_ERR_BAD_ARG;
     }
@@ -288,6 +289,7 @@ int64_t kc_ctx_get_option(const kc_ctx* c, int key) {
         case KC_OPT_XXH_FIN_MODE: return g.xxh_fin_mode;
         case KC_OPT_JOB_PRIME: return g.job_prime;
         case KC_OPT_DSTREAM_BLOCKS: return g.dstream_blocks;
+        case KC_OPT_S2_RSTREAM_CHUNKS: return g.s2_rstream_chunks;
         case KC_OPT_STAGE2_STREAM: return (int64_t)(intptr_t)c->stream2;
         case KC_OPT_LAST_PATH: return c->last_path;
         case KC_OPT_LAST_PRESCAN_UNITS: return c->last_prescan_units;

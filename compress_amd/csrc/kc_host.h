@@ -120,6 +120,7 @@ struct KcCfg {
     int64_t zfast_prescan = -1;           // SpeedFastest: the no-match pre-scan (kc_zstd_prescan.hip): 0 off, 1 on, -1 when the previous batch did not compress
     int64_t job_prime = 1;                // jobs of a WithConcurrentBlocks stream: tables primed from the overlap prefix on the device (0: on the host)
     int64_t dstream_blocks = 512;         // zstd stream reader: blocks per launch (1 .. 4096)
+    int64_t s2_rstream_chunks = 4096;     // S2 stream reader: data chunks per launch (1 .. 4096; the sweep of profiles/s2_stream_reader.json)
     int64_t fuse_raw_xxh = 1;             // frames made of raw blocks only: checksum and payload copy in one pass over the source (kc_xxh64_fin_kernel)
 };
 

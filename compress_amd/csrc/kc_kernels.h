@@ -375,7 +375,7 @@ void kc_launch_zstd_dstream_execute(const KcZsExecParams& P, hipStream_t st);
 void kc_launch_xxh64_stream(const KcZsHashParams& P, hipStream_t st);
 // ---- s2.Reader / s2.Decode as a product (kc_s2_plan_dev.h, kc_s2_plan.hip, kc_s2_decode_all.hip; host side kc_s2_dec_api.cpp) ----
 // Per-stream / per-chunk status classes (include/kcgpu.h KC_S2D_*)
-enum { KCS2D_OK = 0, KCS2D_CORRUPT = 1, KCS2D_CRC = 2, KCS2D_UNSUPPORTED = 3, KCS2D_SIZE = 4, KCS2D_EOF = 5, KCS2D_UNEXPECTED_EOF = 6 };
+enum { KCS2D_OK = 0, KCS2D_CORRUPT = 1, KCS2D_CRC = 2, KCS2D_UNSUPPORTED = 3, KCS2D_SIZE = 4, KCS2D_EOF = 5, KCS2D_UNEXPECTED_EOF = 6, KCS2D_CALLBACK = 7 };
 #define KC_S2C_STORED 1u   // KcS2Chunk.kind: an uncompressed chunk (the body is the bytes), else a block (uvarint length + tags)
 #define KC_S2C_NOCRC 2u    // ... a bare block: nothing stored to compare with
 // One data chunk of one input, written by the plan kernel and consumed by the decode kernel.
@@ -464,6 +464,28 @@ struct KcS2RangeDecodeParams {
     uint32_t* status;            // per covered chunk: KCS2D_OK / KCS2D_CORRUPT / KCS2D_CRC
 };
 void kc_launch_s2_range_decode(const KcS2RangeDecodeParams& P, hipStream_t st);
+// ---- the stream reader s2.NewReader(r).Read / Skip (kc_s2_rstream.hip; host side kc_s2rstream_host.h, kc_s2_rstream_api.cpp) ----
+// One data chunk of one window, written by the host state machine.  Everything is relative to the window: the staged bytes run from
+// the first chunk's body to the end of the last one's, the output is the chunks' decoded bytes back to back.
+struct KcS2WChunk {
+    uint64_t body_off;           // in the staged bytes: behind the chunk's checksum
+    uint64_t out_off;            // in the window's output
+    uint32_t body_len;
+    uint32_t dlen;               // decoded length, from the chunk's own header
+    uint32_t crc;                // the stored (masked) CRC32C
+    uint32_t kind;               // KC_S2C_STORED or 0
+};
+struct KcS2RstreamParams {
+    const uint8_t* in;           // the staged bytes
+    uint64_t in_len;
+    const KcS2WChunk* chunks;
+    uint32_t n_chunks;
+    uint8_t* out;                // the window's output
+    uint64_t out_len;
+    int32_t ignore_crc;
+    uint32_t* status;            // per chunk: KCS2D_OK / KCS2D_CORRUPT / KCS2D_CRC
+};
+void kc_launch_s2_rstream(const KcS2RstreamParams& P, hipStream_t st);
 // default: 2^14 entries; better: long 2^17 + short 2^14 (blocks > 64 KiB), long 2^16 + short 2^13 (all blocks <= 64 KiB)
 static inline size_t kc_s2_table_bytes(int level, uint64_t max_block_len, int variant = 0) {
     // the assembly forms of the better levels take 2^17 + 2^14 entries from 16 KiB on (Snappy-compatible: above 64 KiB; 2^16 + 2^13 below)

@@ -30,23 +30,43 @@ struct KcS2Walk {
     uint32_t status;    // the first header-level error (KCS2D_*), 0: the walk reached the input's end at a chunk boundary
     uint32_t n_chunks;  // data chunks in front of it
     uint64_t total;     // their decoded bytes
-    uint32_t stopped;   // kc_s2_walk_from: more() ended the walk in front of the input's end
+    uint32_t stopped;   // kc_s2_walk_from: KC_S2W_MORE — more() ended the walk in front of the input's end; the partial form: KC_S2W_SHORT*, KC_S2W_SKIPPABLE
+    // where the walk stands when it returns without an error, and the reader state there (the stream reader carries them from call to call)
+    uint64_t pos;
+    uint32_t readHeader, snappy;
+    uint32_t type, chunkLen, dlen;  // KC_S2W_SHORT_DATA / KC_S2W_SKIPPABLE: the chunk at pos; dlen: a data chunk's decoded length
 };
+#define KC_S2W_MORE 1u        // more() said stop: nothing at or behind pos has been read
+#define KC_S2W_SHORT 2u       // partial form: the chunk at pos is not whole and its header says nothing yet that could be acted on
+#define KC_S2W_SHORT_DATA 3u  // partial form: a data chunk at pos whose body is not whole; its header checks passed and dlen is known
+#define KC_S2W_SKIPPABLE 4u   // partial form: a padding, index or other skippable chunk at pos (header present), handed to the caller
 
 // The walk from a given reader state: readHeader / snappy are Reader.readHeader / Reader.snappyFrame at `pos` (a chunk boundary).
 // more(total) is asked before every chunk header is read: false ends the walk there with status 0 and W.stopped set — nothing at
 // or behind `pos` has been read then (the ranged plan, kc_s2_ranges.hip).  emit(index, body_off, body_len, kind, out_rel, dlen, crc)
 // is called for every data chunk in stream order.
-template <class More, class Emit>
+// Partial (the stream reader, kc_s2rstream_host.h): [pos, end) is what a caller holds of a stream that may go on.  A chunk that is
+// not whole is not corrupt: the walk stops in front of it (KC_S2W_SHORT; KC_S2W_SHORT_DATA when it is a data chunk whose header —
+// for a compressed chunk also the uvarint — is there: every check that needs no body has then been made and W.dlen is set, which is
+// all a pending Skip needs).  A skippable chunk is handed over whole or not (KC_S2W_SKIPPABLE): its payload is the caller's to count
+// down.  emit is still called for whole data chunks only.
+template <bool Partial = false, class More, class Emit>
 __host__ __device__ inline KcS2Walk kc_s2_walk_from(const uint8_t* in, uint64_t pos, const uint64_t end, uint32_t max_block, uint32_t max_buf,
                                                     bool readHeader, bool snappy, More more, Emit emit) {
     KcS2Walk W;
-    W.status = KCS2D_OK; W.n_chunks = 0; W.total = 0; W.stopped = 0;
+    W.status = KCS2D_OK; W.n_chunks = 0; W.total = 0; W.stopped = 0; W.type = 0; W.chunkLen = 0; W.dlen = 0;
+    uint64_t hpos = pos;  // (Partial: the header of the chunk in hand, where the walk steps back to)
+    bool rh = readHeader;
     while (pos < end) {  // (nothing left: io.EOF from the 4-byte read, the clean end)
-        if (!more(W.total)) { W.stopped = 1; break; }
-        if (end - pos < 4) { W.status = KCS2D_CORRUPT; break; }
+        if (!more(W.total)) { W.stopped = KC_S2W_MORE; break; }
+        if (end - pos < 4) {
+            if constexpr (Partial) W.stopped = KC_S2W_SHORT; else W.status = KCS2D_CORRUPT;
+            break;
+        }
         const uint32_t type = in[pos];
         const uint32_t chunkLen = (uint32_t)in[pos + 1] | ((uint32_t)in[pos + 2] << 8) | ((uint32_t)in[pos + 3] << 16);
+        hpos = pos;
+        rh = readHeader;
         pos += 4;
         if (!readHeader) {  // before the type switch: a leading padding chunk is corrupt too (reader.go:263-269)
             if (type != 0xffu) { W.status = KCS2D_CORRUPT; break; }
@@ -54,7 +74,26 @@ __host__ __device__ inline KcS2Walk kc_s2_walk_from(const uint8_t* in, uint64_t 
         }
         if (type <= 0x01u) {
             if (chunkLen < 4 || chunkLen > max_buf) { W.status = KCS2D_CORRUPT; break; }
-            if (end - pos < chunkLen) { W.status = KCS2D_CORRUPT; break; }
+            if (end - pos < chunkLen) {
+                if constexpr (Partial) {
+                    uint32_t dl = chunkLen - 4, hdr = 0;
+                    bool known = true;
+                    if (type == 0x00u) {
+                        if (end - pos < 4) known = false;
+                        else if (!kc_s2_decoded_len(in, pos + 4, end, &dl, &hdr)) {
+                            if (end - pos - 4 >= 5) { W.status = KCS2D_CORRUPT; break; }  // five bytes were there: not a matter of more input
+                            known = false;
+                        }
+                    }
+                    if (known && ((snappy && dl > KC_S2_MAX_SNAPPY_BLOCK) || dl > max_block)) { W.status = KCS2D_CORRUPT; break; }
+                    W.stopped = known ? KC_S2W_SHORT_DATA : KC_S2W_SHORT;
+                    W.type = type; W.chunkLen = chunkLen; W.dlen = dl;
+                    pos = hpos; readHeader = rh;
+                } else {
+                    W.status = KCS2D_CORRUPT;
+                }
+                break;
+            }
             const uint32_t crc = (uint32_t)in[pos] | ((uint32_t)in[pos + 1] << 8) | ((uint32_t)in[pos + 2] << 16) | ((uint32_t)in[pos + 3] << 24);
             uint32_t dl = chunkLen - 4, hdr = 0;
             if (type == 0x00u && !kc_s2_decoded_len(in, pos + 4, pos + chunkLen, &dl, &hdr)) { W.status = KCS2D_CORRUPT; break; }
@@ -67,7 +106,11 @@ __host__ __device__ inline KcS2Walk kc_s2_walk_from(const uint8_t* in, uint64_t 
             continue;
         }
         if (type == 0xffu) {  // stream identifier: S2 or Snappy, also in the middle of an input (concatenated streams)
-            if (chunkLen != 6 || end - pos < 6) { W.status = KCS2D_CORRUPT; break; }
+            if (chunkLen != 6) { W.status = KCS2D_CORRUPT; break; }
+            if (end - pos < 6) {
+                if constexpr (Partial) { W.stopped = KC_S2W_SHORT; pos = hpos; readHeader = rh; } else W.status = KCS2D_CORRUPT;
+                break;
+            }
             const uint8_t* m = in + pos;
             if (m[0] == 'S' && m[1] == '2' && m[2] == 's' && m[3] == 'T' && m[4] == 'w' && m[5] == 'O') snappy = false;
             else if (m[0] == 's' && m[1] == 'N' && m[2] == 'a' && m[3] == 'P' && m[4] == 'p' && m[5] == 'Y') snappy = true;
@@ -77,9 +120,18 @@ __host__ __device__ inline KcS2Walk kc_s2_walk_from(const uint8_t* in, uint64_t 
         }
         if (type <= 0x7fu) { W.status = KCS2D_UNSUPPORTED; break; }  // reserved unskippable chunks
         if (chunkLen > KC_S2_MAX_CHUNK) { W.status = KCS2D_UNSUPPORTED; break; }
+        if constexpr (Partial) {
+            W.stopped = KC_S2W_SKIPPABLE; W.type = type; W.chunkLen = chunkLen;
+            pos = hpos; readHeader = rh;
+            break;
+        }
         if (end - pos < chunkLen) { W.status = KCS2D_CORRUPT; break; }  // padding, index and other skippable chunks
         pos += chunkLen;
     }
+    if constexpr (Partial) {
+        if (W.status) { pos = hpos; readHeader = rh; }  // an error leaves the walk in front of the chunk that has it
+    }
+    W.pos = pos; W.readHeader = readHeader ? 1u : 0u; W.snappy = snappy ? 1u : 0u;
     return W;
 }
 

@@ -584,11 +584,13 @@ def NewWriter(w, *opts, **kw):
 # ---------------------------------------------------------------------------------------------------------------------
 # s2.Reader / s2.Decode (s2/reader.go, s2/decode.go) over the device path: whole inputs, in batches.  Every input is decoded
 # as io.ReadAll(s2.NewReader(input)) would; ranged reads go through Reader.ReadRanges and the cursor s2.NewReadSeeker returns.
-# The methods Read, Skip, ReadSeeker, ReadByte of Reader itself and skippable-chunk callbacks stay with the reference.
+# The methods Read, Skip, ReadSeeker, ReadByte of Reader itself raise; reading one stream piece by piece, with skippable-chunk
+# callbacks, is StreamReader (NewStreamReader) further down.
 # ---------------------------------------------------------------------------------------------------------------------
 class S2DecodeError(ValueError):
     """The reader refused an input.  `name` is the class of the reference's error: KC_S2D_CORRUPT (ErrCorrupt), KC_S2D_CRC (ErrCRC),
-    KC_S2D_UNSUPPORTED (ErrUnsupported), or KC_S2D_SIZE_EXCEEDED (an input too large for the scratch ceiling of a host-buffer call)."""
+    KC_S2D_UNSUPPORTED (ErrUnsupported), KC_S2D_SIZE_EXCEEDED (an input too large for the scratch ceiling of a host-buffer call),
+    KC_S2D_EOF / KC_S2D_UNEXPECTED_EOF (ranged reads, Skip), or KC_S2D_CALLBACK (the stream reader: a skippable-chunk callback failed)."""
 
     def __init__(self, status):
         self.status = int(status)
@@ -827,6 +829,207 @@ class Reader:
 def NewReader(r, *opts, **kw):
     """s2.NewReader(r, opts...) (reader.go:31)."""
     return Reader(r, *opts, **kw)
+
+
+class StreamReader:
+    """s2.NewReader(r) as a stream reader (reader.go:249-405, :674-842, :1044): Read / Skip / ReadByte / ReadSeeker decode r piece by
+    piece in bounded memory (kc_s2_rstream_feed: up to KC_OPT_S2_RSTREAM_CHUNKS data chunks per launch, one wave per chunk).  It takes
+    the reader options of Reader.  skippable: {id: fn} (ReaderSkippableCB, reader.go:109; 0x80 <= id <= 0xfd) — fn(reader) gets a
+    file-like object over the chunk's content; an exception it raises aborts the stream and is re-raised.  batch_bytes: how much is
+    pulled from r, and decoded, at a time.  s2.Reader stays the reader for whole inputs and batches."""
+
+    def __init__(self, r, *opts, skippable=None, batch_bytes=32 << 20, device=0, stream=None):
+        from . import zstd as _zstd
+        L = _lib.load()
+        self._opts = opts
+        self._o = C.c_void_p(L.kc_s2_ropts_default())
+        if not self._o:
+            raise MemoryError("kc_s2_ropts_default")
+        for op in opts:
+            op(self)
+        for id in (skippable or {}):
+            if not 0x80 <= int(id) <= 0xfd:
+                raise ValueError("ReaderSkippableCB: Invalid id provided, must be 0x80-0xfd (inclusive)")
+        self._skippable = dict(skippable or {})
+        self._device, self._stream = device, stream
+        self._batch_bytes = batch_bytes
+        self._ctx = _lib.Context(device, stream)
+        self._cb_err = None
+        self._parts = {}
+        self._fn = _lib.S2_SKIPPABLE_FN(self._on_piece)  # (kept alive as long as the stream)
+        self._r = r
+        self._sb = _zstd.StreamBuffer(self._new, L.kc_s2_rstream_feed, L.kc_s2_rstream_free, r, batch_bytes, min_cap=_MAX_BLOCK,
+                                      what="s2 stream reader")
+
+    def ctx(self):
+        return self._ctx
+
+    def _new(self):
+        L = self._ctx.L
+        h = L.kc_s2_rstream_new(self._ctx.h, self._o)
+        if h:
+            for id in self._skippable:
+                self._ctx.check(L.kc_s2_rstream_on_skippable(h, int(id), self._fn, None))
+        return h
+
+    def _on_piece(self, user, id, piece, n, left):
+        try:
+            self._parts.setdefault(id, []).append(C.string_at(piece, n) if n else b"")
+            if left == 0:
+                import io
+                content = b"".join(self._parts.pop(id))
+                self._skippable[id](io.BytesIO(content))
+            return 0
+        except BaseException as e:  # noqa: BLE001 (it is raised again where the stream's error surfaces)
+            self._cb_err = e
+            return 1
+
+    def _buffer(self):
+        if self._sb is None:
+            raise ValueError("s2: StreamReader used after Close")
+        return self._sb
+
+    def _raise(self, status):
+        if status == 7 and self._cb_err is not None:
+            raise self._cb_err
+        raise S2DecodeError(status)
+
+    def Read(self, p):
+        """Reader.Read (reader.go:249): fills p from the decoded stream and returns the count (fewer than len(p) only at the stream's
+        end or in front of its error); 0 at the end.  S2DecodeError is raised only once the bytes in front of the error have been
+        returned.  An empty p with nothing buffered advances to the next data chunk and fires the callbacks on the way."""
+        sb = self._buffer()
+        if len(p) == 0:
+            if not sb.fill() and sb.status:
+                self._raise(sb.status)
+            return 0
+        n = sb.read_into(p)
+        if n == 0 and sb.status:
+            self._raise(sb.status)
+        return n
+
+    def Skip(self, n):
+        """Reader.Skip (reader.go:674): n decoded bytes forward — buffered bytes first, the rest by the chunk headers (the bodies of
+        the chunks passed are not decoded).  Raises only if the skip could not be completed: KC_S2D_UNEXPECTED_EOF when the input ends
+        first, else the class of the error met; an error behind a completed skip waits for the next Read."""
+        if n < 0:
+            raise ValueError("attempted negative skip")
+        sb = self._buffer()
+        n -= sb.drop(n)
+        if n == 0:
+            return
+        if sb.status:
+            self._raise(sb.status)
+        if sb.done:
+            raise S2DecodeError(6)
+        L = self._ctx.L
+        self._ctx.check(L.kc_s2_rstream_skip(sb.handle, int(n)))
+        while L.kc_s2_rstream_skip_left(sb.handle) and not sb.buffered() and not sb.status and not sb.done:
+            sb.step()
+        if L.kc_s2_rstream_skip_left(sb.handle):
+            self._raise(sb.status or 6)
+
+    def ReadByte(self):
+        """Reader.ReadByte (reader.go:1044); raises EOFError at the end of the stream."""
+        p = bytearray(1)
+        if self.Read(p) != 1:
+            raise EOFError("EOF")
+        return p[0]
+
+    def Reset(self, r):
+        """Reader.Reset (reader.go:177): read from r from now on; options and callbacks stay, and so do the stream's device buffers and
+        the host buffer (kc_s2_rstream_reset, which also takes KC_OPT_S2_RSTREAM_CHUNKS as the context holds it now)."""
+        sb = self._buffer()
+        self._ctx.check(self._ctx.L.kc_s2_rstream_reset(sb.handle))
+        self._cb_err, self._parts, self._r = None, {}, r
+        sb.restart(r)
+
+    def ReadSeeker(self, random=False, index=None):
+        """Reader.ReadSeeker (reader.go:864-1000).  random=False: a forward-only seeker over this stream (reader.go:968-975).
+        random=True: r must be seekable (ErrCantSeek otherwise); the whole-input s2.ReadSeeker over r is returned."""
+        if not random:
+            ix = None
+            if index is not None and len(index) != 0:
+                ix = Index()
+                try:
+                    ix.Load(index)
+                except S2DecodeError as e:
+                    raise ErrCantSeek("loading index returned: " + str(e))
+            return _ForwardSeeker(self, ix)
+        if not hasattr(self._r, "seek"):
+            raise ErrCantSeek("input stream isn't seekable")
+        self._r.seek(0)
+        return ReadSeeker(self._r, *self._opts, random=True, index=index, device=self._device, stream=self._stream)
+
+    def Close(self):
+        """Releases the stream, its device buffers and the context."""
+        sb, self._sb = self._sb, None
+        if sb is not None:
+            sb.close()
+        c, self._ctx = self._ctx, None
+        if c is not None:
+            c.close()
+
+    def __del__(self):
+        try:
+            self.Close()
+            if getattr(self, "_o", None):
+                _lib.load().kc_s2_ropts_free(self._o)
+                self._o = None
+        except Exception:
+            pass
+
+
+class _ForwardSeeker:
+    """The forward-only ReadSeeker of a StreamReader (reader.go:968-975): Seek forward is Skip, a backward Seek and — without an
+    index — SeekEnd are refused with KC_S2D_UNSUPPORTED; ReadAt moves the cursor (reader.go:859)."""
+
+    def __init__(self, rd, index):
+        self._rd, self._index, self._pos = rd, index, 0
+
+    def Seek(self, offset, whence=0):
+        if whence == SeekStart:
+            a = offset
+        elif whence == SeekCurrent:
+            a = self._pos + offset
+        elif whence == SeekEnd:
+            if self._index is None:
+                raise S2DecodeError(3)  # ErrUnsupported (reader.go:941)
+            a = self._index.TotalUncompressed + offset
+        else:
+            raise S2DecodeError(3)
+        if a < 0:
+            raise ValueError("seek before start of file")
+        if a < self._pos:
+            raise S2DecodeError(3)  # forward-only (reader.go:975)
+        self._rd.Skip(a - self._pos)
+        self._pos = a
+        return a
+
+    def Read(self, p):
+        n = self._rd.Read(p)
+        self._pos += n
+        return n
+
+    def ReadAt(self, p, off):
+        if off < 0:
+            raise ValueError("seek before start of file")
+        self.Seek(off, SeekStart)
+        return self.Read(p)
+
+    def Skip(self, n):
+        self._rd.Skip(n)
+        self._pos += n
+
+    def ReadByte(self):
+        b = self._rd.ReadByte()
+        self._pos += 1
+        return b
+
+
+def NewStreamReader(r, *opts, **kw):
+    """s2.NewReader(r, opts...) (reader.go:31) for reading r as a stream: StreamReader."""
+    return StreamReader(r, *opts, **kw)
 
 
 def IndexStream(r):

@@ -591,15 +591,16 @@ class StreamBuffer:
     dst, dst_cap, consumed*, produced*, status*) -> kc_status (kc_zstd_dstream_feed's signature behind the handle) and free(handle).
     It pulls r.read(batch_bytes), keeps the tail the decoder has not consumed, and hands the decoded bytes out in slices."""
 
-    def __init__(self, new, feed, free, r, batch_bytes=32 << 20):
+    def __init__(self, new, feed, free, r, batch_bytes=32 << 20, min_cap=128 << 10, what="zstd stream decoder"):
         self._feed, self._free = feed, free
+        self._what = what   # names the decoder in error texts
         self._h = new()
         if not self._h:
-            raise MemoryError("zstd stream decoder: new() failed")
+            raise MemoryError("%s: new() failed" % what)
         self._r = r
         self._batch = max(int(batch_bytes), 1)
         self._in, self._pos, self._eof = b"", 0, False
-        self._cap = max(self._batch, 128 << 10)  # (no block's bound is above 128 KiB)
+        self._cap = max(self._batch, int(min_cap))  # (zstd: no block's bound is above 128 KiB; another format names its own)
         self._out = C.create_string_buffer(self._cap)
         self._lo = self._hi = 0
         self.status = 0     # the class of the stream's error, once everything in front of it has been decoded
@@ -610,31 +611,65 @@ class StreamBuffer:
         if h:
             self._free(h)
 
+    @property
+    def handle(self):
+        """The decoder's handle (what new() returned), for calls beside feed."""
+        return self._h
+
+    def buffered(self):
+        """Decoded bytes held and not yet handed out."""
+        return self._hi - self._lo
+
+    def drop(self, n):
+        """Discards up to n of the buffered bytes; returns how many."""
+        k = min(int(n), self._hi - self._lo)
+        self._lo += k
+        return k
+
+    def restart(self, r):
+        """The same handle and buffer for a new input r: the caller has reset the decoder behind the handle."""
+        self._r = r
+        self._in, self._pos, self._eof = b"", 0, False
+        self._lo = self._hi = 0
+        self.status, self.done = 0, False
+
+    def fill(self):
+        """Decodes until there are bytes to hand out (at once when some are buffered); False at the stream's end or at its error."""
+        return self._more()
+
+    def step(self):
+        """One turn of the loop behind read_into, for a caller that drives the decoder without taking bytes (a skip)."""
+        self._step()
+
+    def _step(self):
+        """One call of the decoder on what is held; when it neither takes nor gives anything, more input from r (or the end)."""
+        consumed, produced, status = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        n = len(self._in) - self._pos
+        src = C.cast(C.c_char_p(self._in), C.c_void_p).value + self._pos if n else None
+        rc = self._feed(self._h, src, n, int(self._eof), C.addressof(self._out), self._cap, C.byref(consumed), C.byref(produced), C.byref(status))
+        if rc != 0:
+            raise _lib.KcError(rc, "%s: feed" % self._what)
+        self._pos += consumed.value
+        self._lo, self._hi = 0, produced.value
+        self.status = status.value
+        if consumed.value or produced.value or status.value:
+            return
+        if self._eof:  # nothing left and nothing asked for: the clean end
+            self.done = True
+            return
+        chunk = self._r.read(self._batch)
+        if chunk:
+            self._in = self._in[self._pos:] + bytes(chunk)
+            self._pos = 0
+        else:
+            self._eof = True
+
     def _more(self):
         """Decodes until there are bytes to hand out; False at the stream's end or at its error."""
-        consumed, produced, status = C.c_uint64(), C.c_uint64(), C.c_uint32()
         while self._lo == self._hi:
             if self.status or self.done:
                 return False
-            n = len(self._in) - self._pos
-            src = C.cast(C.c_char_p(self._in), C.c_void_p).value + self._pos if n else None
-            rc = self._feed(self._h, src, n, int(self._eof), C.addressof(self._out), self._cap, C.byref(consumed), C.byref(produced), C.byref(status))
-            if rc != 0:
-                raise _lib.KcError(rc, "zstd stream decoder: feed")
-            self._pos += consumed.value
-            self._lo, self._hi = 0, produced.value
-            self.status = status.value
-            if consumed.value or produced.value or status.value:
-                continue
-            if self._eof:  # nothing left and nothing asked for: the clean end
-                self.done = True
-                return False
-            chunk = self._r.read(self._batch)
-            if chunk:
-                self._in = self._in[self._pos:] + bytes(chunk)
-                self._pos = 0
-            else:
-                self._eof = True
+            self._step()
         return True
 
     def read_into(self, p):

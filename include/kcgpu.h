@@ -202,6 +202,7 @@ typedef enum {
     KC_OPT_HOST_ROLL_MIB = 34,       /* KC_HOST_ROLL_MIB          rolling pipeline: sub-batch size (0: a quarter of the call's input — SpeedBetterCompression and S2: half —, 64 MiB .. 1 GiB) */
     KC_OPT_S2_HOOK_HOST_FIRST = 35,  /* KC_S2_HOOK_HOST_FIRST     kc_s2_encode_block: how many callers at a time are left to the host's built-in encoder (they get -1) before the overflow goes to the device: -1 (default) the host's hardware threads, 0 every caller to the device (see kc_s2_encode_block) */
     KC_OPT_DSTREAM_BLOCKS = 36,      /* (no variable)             zstd stream reader (kc_zstd_dstream_new): blocks per launch, 1 .. 4096 (default 512); at 1 every block is a launch of its own */
+    KC_OPT_S2_RSTREAM_CHUNKS = 37,   /* (no variable)             S2 stream reader (kc_s2_rstream_new): data chunks per launch, 1 .. 4096 (default 4096: the smallest value within the spread of the best rate at 64 KiB blocks, profiles/s2_stream_reader.json); at 1 every chunk is a launch of its own */
     KC_OPT_LAST_PRESCAN_UNITS = 102, /* read-only: units of the last batch the pre-scan settled */
     KC_OPT_LAST_PATH = 100,          /* read-only: KC_PATH_HBM / KC_PATH_LDS the last batch ran on */
     KC_OPT_LAST_BATCHES = 101        /* read-only: device batches the last kc_zstd_encode_units_dev / kc_s2_encode_*_dev call was cut into */
@@ -450,7 +451,8 @@ enum {
     KC_S2D_UNSUPPORTED = 3,    /* ErrUnsupported */
     KC_S2D_SIZE_EXCEEDED = 4,  /* a limit of this library: host-buffer calls, an input that does not fit the scratch ceiling alone */
     KC_S2D_EOF = 5,            /* ranged reads: io.EOF — the input ended inside the range, got < len */
-    KC_S2D_UNEXPECTED_EOF = 6  /* ranged reads: io.ErrUnexpectedEOF — the input ended in front of the range (Reader.Skip, Index.Find) */
+    KC_S2D_UNEXPECTED_EOF = 6, /* ranged reads: io.ErrUnexpectedEOF — the input ended in front of the range (Reader.Skip, Index.Find) */
+    KC_S2D_CALLBACK = 7        /* stream reader: a skippable-chunk callback returned non-zero (the reference returns the callback's error) */
 };
 /* kc_s2_decode_streams[_dev] == io.ReadAll(s2.NewReader(input, options)) for every input (s2/reader.go:249-405).  src: the inputs,
  * concatenated; in_off: n + 1 ascending offsets into it.  Input i is any concatenation of .s2 or Snappy-framed streams, as
@@ -555,6 +557,53 @@ kc_status kc_s2_read_ranges_dev(kc_ctx* ctx, const kc_s2_ropts* o, const uint8_t
 kc_status kc_s2_read_ranges(kc_ctx* ctx, const kc_s2_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n_streams,
                             const kc_s2_index* const* index, const uint32_t* req_stream, const uint64_t* req_off, const uint64_t* req_len,
                             uint32_t m, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* got, uint32_t* status);
+/* ---- s2.NewReader(r) as a stream reader: Read / Skip / ReadByte / skippable-chunk callbacks (s2/reader.go:249-405 Read, :190-198
+ * readFull, :200-246 skippable, :109 ReaderSkippableCB, :674-842 Skip, :177 Reset) ----
+ * One stream at a time is fed piece by piece from host memory and decoded in bounded memory: a .s2 file larger than memory can be read.
+ * The device keeps one window — the staged compressed bytes of up to KC_OPT_S2_RSTREAM_CHUNKS data chunks and their decoded bytes —,
+ * decodes it with one wave per chunk and copies the deliverable prefix straight to the caller's dst.  One window at a time, synchronous.
+ *
+ * kc_s2_rstream_new (NewReader): a fresh stream on `ctx` with a copy of the options.  kc_s2_rstream_reset (Reset, :177): the same
+ * object and the same device buffers for a new stream; options and callbacks stay.  Both take KC_OPT_S2_RSTREAM_CHUNKS as the
+ * context holds it at that moment.  A copy or launch that fails is no verdict on the input: feed returns that kc_status, and every
+ * later feed returns it again until the stream is reset.  kc_s2_rstream_free releases the stream and its device buffers.
+ * kc_s2_rstream_feed (Read, :249-405): src[0 .. n) is what the caller holds of the stream from the first byte not yet consumed;
+ * eof != 0 says nothing follows it.  src and dst are host memory.  KC_ERR_BAD_ARG while the context has a pending batch or job.
+ *   Consuming: a data chunk that is to be decoded is consumed only when whole (fewer than 4 + MaxEncodedLen(max block) + 4 bytes are
+ *   ever left unconsumed), a stream identifier when whole.  The payload of a skippable, padding or index chunk and the body of a data
+ *   chunk that lies wholly inside a pending skip are counted down piece by piece and never buffered; for such a data chunk only the
+ *   header is needed, for type 0x00 also the uvarint.
+ *   Producing: dst[0 .. *produced) receives as many whole chunks, in stream order, as fit dst_cap by their stated decoded length, at
+ *   most the window limit per launch; nothing is written at or behind dst + *produced.  KC_ERR_DST_TOO_SMALL when the next chunk to
+ *   hand out does not fit dst_cap and nothing else can be produced: nothing is consumed or written then and the stream stays usable.
+ *   Errors: *status is 0 or the KC_S2D_* class of the first error in stream order — the reference's sequential behaviour, which
+ *   kc_s2_decode_streams deliberately does not have: the bytes of every chunk in front of the error are produced first, in the same
+ *   call or earlier ones, and the stream stays failed: later calls return the class and nothing else.  Inside a chunk the order is
+ *   that of kc_s2_decode_streams: DecodedLen, Snappy's 64 KiB limit, the block size limit, the decode, the CRC.
+ *   End of input: eof at a chunk boundary, an empty input included, is the clean end (consumed == n, produced == 0, status 0;
+ *   :259-261); eof with 1-3 stray bytes or inside any chunk is KC_S2D_CORRUPT (readFull, :190-198); eof while a skip is pending is
+ *   KC_S2D_UNEXPECTED_EOF (:700-705).  The same bytes without eof: the call waits — status 0, consumption stops at the boundary.
+ * kc_s2_rstream_skip (Skip, :674-842) adds n to the pending skip, kc_s2_rstream_skip_left returns what is left of it; the following
+ * feeds pass the chunks wholly inside the skip by their headers — their bodies are not staged, decoded or CRC-checked — and decode
+ * the chunk that holds the skip's end whole, checked over the whole chunk; only its bytes behind the skip go to dst and must fit
+ * dst_cap.  Verdicts and deviations are those of kc_s2_read_ranges: (1) no body of a skipped chunk is read (the reference CRC-checks
+ * some skipped uncompressed chunks, :799); (2) Snappy's 64 KiB limit applies to passed chunks too; (3) a CRC mismatch in the partly
+ * skipped chunk is KC_S2D_CRC and honours ReaderIgnoreCRC (the reference says ErrCorrupt there, :757-760).
+ * kc_s2_rstream_on_skippable (ReaderSkippableCB, :109): id outside 0x80 .. 0xfd is KC_ERR_BAD_ARG, a null fn removes the callback.  A
+ * chunk with a callback is handed over as pieces, in order: fn(user, id, piece, n, left) with `left` the bytes of the chunk still to
+ * come; a chunk of length 0 gets one call with n == 0, left == 0.  The callback runs inside feed, and only after every decoded byte in
+ * front of that chunk has been returned by an earlier feed (a window never reaches past such a chunk): a caller that asks for more
+ * only when it has handed everything out sees the reference's lazy order.  A non-zero return fails the stream with KC_S2D_CALLBACK. */
+typedef struct kc_s2_rstream kc_s2_rstream;
+typedef int (*kc_s2_skippable_fn)(void* user, uint8_t id, const uint8_t* piece, uint64_t n, uint64_t left);
+kc_s2_rstream* kc_s2_rstream_new(kc_ctx* ctx, const kc_s2_ropts* o);
+kc_status kc_s2_rstream_feed(kc_s2_rstream* s, const uint8_t* src, uint64_t n, int eof, uint8_t* dst, uint64_t dst_cap,
+                             uint64_t* consumed, uint64_t* produced, uint32_t* status);
+kc_status kc_s2_rstream_skip(kc_s2_rstream* s, uint64_t n);
+uint64_t kc_s2_rstream_skip_left(const kc_s2_rstream* s);
+kc_status kc_s2_rstream_on_skippable(kc_s2_rstream* s, uint8_t id, kc_s2_skippable_fn fn, void* user);
+kc_status kc_s2_rstream_reset(kc_s2_rstream* s);
+void kc_s2_rstream_free(kc_s2_rstream* s);
 /* Single-block form with the WriterCustomEncoder contract (s2/writer.go:1053-1064): no varint header;
  * returns bytes used, 0 = incompressible (store raw), <0 = fall back to the built-in encoder.
  * "The function should expect to be called concurrently" (writer.go:1058; s2.Writer calls it from one goroutine per block,

@@ -25,6 +25,8 @@
 #include "../../compress_amd/csrc/kc_s2_decode_all.hip"
 #include "../../compress_amd/csrc/kc_s2_ranges.hip"
 #include "../../compress_amd/csrc/kc_s2_index.cpp"   // (host code: s2.Index, exported from this library as from the product)
+#include "../../compress_amd/csrc/kc_s2_rstream.hip"
+#include "../../compress_amd/csrc/kc_s2rstream_host.h"
 
 // s2.Reader / s2.Decode over n inputs on the emulator: the plan kernel (both passes), the decode kernel with its CRC, the verdict per
 // input (first failing chunk in stream order, else the plan's error) and the zero-fill of the failed ranges — kc_s2_dec_api.cpp's
@@ -87,6 +89,31 @@ struct KcemuZsDevice : KcZsDevice {
 struct KcemuZsStream {
     KcemuZsDevice dev;
     KcZsStream s;
+};
+
+// The S2 stream reader's device over plain memory, in the same way.
+struct KcemuS2rDevice : KcS2rDevice {
+    void* buf[B_N] = {nullptr};
+    size_t cap[B_N] = {0};
+    int reserve(int which, size_t bytes, void** p) override {
+        if (cap[which] < bytes || !buf[which]) {
+            free(buf[which]);
+            buf[which] = malloc(bytes ? bytes : 1);
+            cap[which] = bytes;
+            if (buf[which]) memset(buf[which], 0xA7, bytes);
+        }
+        *p = buf[which];
+        return buf[which] ? 0 : -6;
+    }
+    int h2d(void* d, const void* h, size_t n) override { if (n) memcpy(d, h, n); return 0; }
+    int d2h(void* h, const void* d, size_t n) override { if (n) memcpy(h, d, n); return 0; }
+    void launch(const KcS2RstreamParams& P) override { kc_launch_s2_rstream(P, nullptr); }
+    int sync() override { return 0; }
+    ~KcemuS2rDevice() override { for (void* b : buf) free(b); }
+};
+struct KcemuS2rStream {
+    KcemuS2rDevice dev;
+    KcS2rStream s;
 };
 
 extern "C" {
@@ -230,6 +257,27 @@ int kcemu_zstd_dstream_feed(void* h, const uint8_t* src, uint64_t n, int eof, ui
 }
 int kcemu_zstd_dstream_reset(void* h) { ((KcemuZsStream*)h)->s.reset(); return 0; }
 void kcemu_zstd_dstream_free(void* h) { delete (KcemuZsStream*)h; }
+
+// s2.NewReader(r).Read / Skip on the emulator: kc_s2_rstream_new / _feed / _skip / _skip_left / _on_skippable / _reset / _free of
+// include/kcgpu.h without the context — the state machine of kc_s2rstream_host.h over KcemuS2rDevice.  chunks: data chunks per launch
+// (KC_OPT_S2_RSTREAM_CHUNKS); max_buf: MaxEncodedLen(max_block) + 4.
+void* kcemu_s2_rstream_new(uint32_t max_block, uint32_t max_buf, int ignore_crc, int ignore_id, uint32_t chunks) {
+    if (chunks < 1 || chunks > 4096) return nullptr;
+    KcemuS2rStream* z = new KcemuS2rStream();
+    z->s.dev = &z->dev;
+    z->s.o.max_block = max_block; z->s.o.max_buf = max_buf; z->s.o.ignore_crc = ignore_crc; z->s.o.ignore_id = ignore_id; z->s.o.chunks = chunks;
+    z->s.start();
+    return z;
+}
+int kcemu_s2_rstream_feed(void* h, const uint8_t* src, uint64_t n, int eof, uint8_t* dst, uint64_t dst_cap, uint64_t* consumed, uint64_t* produced,
+                          uint32_t* status) {
+    return ((KcemuS2rStream*)h)->s.feed(src, n, eof, dst, dst_cap, consumed, produced, status);
+}
+int kcemu_s2_rstream_skip(void* h, uint64_t n) { ((KcemuS2rStream*)h)->s.skip_left += n; return 0; }
+uint64_t kcemu_s2_rstream_skip_left(void* h) { return ((KcemuS2rStream*)h)->s.skip_left; }
+int kcemu_s2_rstream_on_skippable(void* h, uint8_t id, kc_s2_skippable_fn fn, void* user) { return ((KcemuS2rStream*)h)->s.on_skippable(id, fn, user); }
+int kcemu_s2_rstream_reset(void* h) { ((KcemuS2rStream*)h)->s.reset(); return 0; }
+void kcemu_s2_rstream_free(void* h) { delete (KcemuS2rStream*)h; }
 
 int kcemu_s2_decode_streams(const uint8_t* src, const uint64_t* in_off, uint32_t n, uint32_t max_block, uint32_t max_buf, int ignore_crc, int ignore_id,
                             uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* bound, uint32_t* status) {

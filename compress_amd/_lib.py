@@ -59,6 +59,9 @@ SYMBOLS = [
     "kc_s2_read_ranges_dev", "kc_s2_read_ranges",
     "kc_s2_rstream_new", "kc_s2_rstream_feed", "kc_s2_rstream_skip", "kc_s2_rstream_skip_left", "kc_s2_rstream_on_skippable", "kc_s2_rstream_reset",
     "kc_s2_rstream_free",
+    "kc_flate_ropts_default", "kc_flate_ropts_free", "kc_flate_ropts_dict", "kc_flate_ropts_multistream",
+    "kc_flate_inflate_dev", "kc_flate_inflate", "kc_flate_inflate_bound_dev", "kc_flate_inflate_bound",
+    "kc_gzip_inflate_dev", "kc_gzip_inflate", "kc_gzip_inflate_bound_dev", "kc_gzip_inflate_bound",
     "kc_probe_table_pattern", "kc_probe_pcie", "kc_ctx_trim", "kc_device_trim", "kc_s2_hook_declined", "kc_create_error", "kc_host_alloc", "kc_host_free",
 ]
 
@@ -273,6 +276,22 @@ def load():
     L.kc_s2_rstream_reset.restype = C.c_int
     L.kc_s2_rstream_free.argtypes = [vp]
     L.kc_s2_rstream_free.restype = None
+    L.kc_flate_ropts_default.argtypes = []
+    L.kc_flate_ropts_default.restype = vp
+    L.kc_flate_ropts_free.argtypes = [vp]
+    L.kc_flate_ropts_free.restype = None
+    L.kc_flate_ropts_dict.argtypes = [vp, vp, u64]
+    L.kc_flate_ropts_dict.restype = C.c_int
+    L.kc_flate_ropts_multistream.argtypes = [vp, C.c_int]
+    L.kc_flate_ropts_multistream.restype = C.c_int
+    for n in ("kc_flate_inflate_dev", "kc_flate_inflate", "kc_gzip_inflate_dev", "kc_gzip_inflate"):
+        f = getattr(L, n)
+        f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, u64, vp, vp, vp]
+        f.restype = C.c_int
+    for n in ("kc_flate_inflate_bound_dev", "kc_flate_inflate_bound", "kc_gzip_inflate_bound_dev", "kc_gzip_inflate_bound"):
+        f = getattr(L, n)
+        f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp]
+        f.restype = C.c_int
     L.kc_s2_encode_block.argtypes = [vp, vp, u64, vp, u64]
     L.kc_s2_encode_block.restype = C.c_int64
     L.kc_s2_hook_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]

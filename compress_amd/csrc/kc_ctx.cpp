@@ -317,6 +317,11 @@ static void ctx_free_scratch(kc_ctx* c) {
         b.p = nullptr;
         b.cap = 0;
     }
+    for (DevBuf& b : c->fl) {  // flate / gzip readers (kc_flate_api.cpp)
+        if (b.p) (void)hipFree(b.p);
+        b.p = nullptr;
+        b.cap = 0;
+    }
     // what the context remembered about the freed buffers' contents
     c->predef_ready = false;
     c->tab_owner = 0;

@@ -1,7 +1,7 @@
 #pragma once
 // kc_host.h — internal header of the host side of the C ABI (include/kcgpu.h): the context, its scratch buffers and the batch
 // records shared by the translation units kc_ctx.cpp (options, context), kc_batch.cpp (the zstd device pipeline), kc_zstd_host.cpp
-// (host-buffer entry points), kc_jobs.cpp (WithConcurrentBlocks), kc_s2_api.cpp (S2), kc_zstd_dec_api.cpp (DecodeAll), kc_zstd_dstream_api.cpp (the stream reader), kc_s2_dec_api.cpp (s2.Reader) and kc_hook.cpp
+// (host-buffer entry points), kc_jobs.cpp (WithConcurrentBlocks), kc_s2_api.cpp (S2), kc_zstd_dec_api.cpp (DecodeAll), kc_zstd_dstream_api.cpp (the stream reader), kc_s2_dec_api.cpp (s2.Reader), kc_flate_api.cpp (flate / gzip readers) and kc_hook.cpp
 // (the WriterCustomEncoder hook).
 // Not installed: the boundary is include/kcgpu.h.
 // There is deliberately NO CPU fallback in this library: when the device path cannot serve a
@@ -176,6 +176,7 @@ struct kc_ctx {
     DevBuf zd[20];                       // zstd.Decoder.DecodeAll (kc_zstd_dec_api.cpp): plan, frame records, staging, literal scratch
     DevBuf s2d[13];                      // s2.Reader / s2.Decode (kc_s2_dec_api.cpp): plan results, chunk records, chunk verdicts; from [8] on the
                                          // ranged reads (kc_s2_ranges_api.cpp): requests, their plans, chunk records, verdicts, clip slots
+    DevBuf fl[8];                        // flate / gzip inflate (kc_flate_api.cpp): offsets, the sizing pass's results, the write pass's verdicts, the dictionary
     DevBuf unit_done, probe_rel;         // no-match pre-scan (kc_zstd_prescan.hip): per-unit verdicts; the probe positions of one block
     int probe_bs = 0;                    // block size probe_rel was built for
     uint32_t probe_n = 0;

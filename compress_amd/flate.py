@@ -1,0 +1,226 @@
+"""compress/flate's reader on the device: raw DEFLATE (RFC 1951) inflated in batches of independent inputs, one wave per input
+(include/kcgpu.h kc_flate_inflate*; kernels compress_amd/csrc/kc_flate_inflate.hip).  There is no CPU fallback."""
+import ctypes as C
+
+from . import _lib
+
+FL_OK, FL_CORRUPT, FL_EOF, FL_HEADER, FL_CHECKSUM, FL_SIZE_EXCEEDED = 0, 1, 2, 3, 4, 5
+FL_NAMES = {0: "KC_FL_OK", 1: "KC_FL_CORRUPT", 2: "KC_FL_EOF", 3: "KC_FL_HEADER", 4: "KC_FL_CHECKSUM", 5: "KC_FL_SIZE_EXCEEDED"}
+
+
+class InflateError(ValueError):
+    """An input was refused.  `status` is its KC_FL_* class, `name` that class's name."""
+
+    def __init__(self, status):
+        self.status = int(status)
+        self.name = FL_NAMES.get(self.status, str(self.status))
+        super().__init__("flate: %s" % self.name)
+
+
+class CorruptInputError(InflateError):
+    """flate.CorruptInputError (inflate.go:33-38); the offset is not reported."""
+
+    def __init__(self, status=FL_CORRUPT):
+        super().__init__(status)
+
+
+class ErrUnexpectedEOF(InflateError, EOFError):
+    """io.ErrUnexpectedEOF: the input ended inside a block."""
+
+    def __init__(self, status=FL_EOF):
+        super().__init__(status)
+
+
+_ERRORS = {FL_CORRUPT: CorruptInputError, FL_EOF: ErrUnexpectedEOF}
+
+
+def error_of(status, table=_ERRORS):
+    return table.get(int(status), InflateError)(int(status))
+
+
+class Batch:
+    """The batch entry points of one format over one options object and one device context (gzip.py shares it)."""
+
+    def __init__(self, prefix, errors, dict=None, multistream=True, device=0, stream=None):
+        L = _lib.load()
+        self._prefix, self._errors = prefix, errors
+        self._o = C.c_void_p(L.kc_flate_ropts_default())
+        if not self._o:
+            raise MemoryError("kc_flate_ropts_default")
+        if dict:
+            d = bytes(dict)
+            if L.kc_flate_ropts_dict(self._o, d, len(d)) != 0:
+                raise ValueError("flate: dictionary rejected")
+        L.kc_flate_ropts_multistream(self._o, 1 if multistream else 0)
+        self._device, self._stream, self._ctx = device, stream, None
+
+    def ctx(self):
+        if self._ctx is None:
+            self._ctx = _lib.Context(self._device, self._stream)
+        return self._ctx
+
+    def error(self, status):
+        return error_of(status, self._errors)
+
+    def bounds(self, src_ptr, in_off, dev):
+        import numpy as np
+        ctx = self.ctx()
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = len(in_off) - 1
+        bound, status, used = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint64)
+        fn = getattr(ctx.L, self._prefix + "_bound" + ("_dev" if dev else ""))
+        ctx.check(fn(ctx.h, self._o, src_ptr, in_off.ctypes.data, n, bound.ctypes.data, status.ctypes.data, used.ctypes.data))
+        return bound[:n], status[:n], used[:n]
+
+    def inflate(self, src_ptr, in_off, dst_ptr, dst_cap, dev):
+        import numpy as np
+        ctx = self.ctx()
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = len(in_off) - 1
+        out_off, status, used = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint64)
+        fn = getattr(ctx.L, self._prefix + ("_dev" if dev else ""))
+        ctx.check(fn(ctx.h, self._o, src_ptr, in_off.ctypes.data, n, dst_ptr, int(dst_cap), out_off.ctypes.data, status.ctypes.data, used.ctypes.data))
+        return out_off, status[:n], used[:n]
+
+    def all_host(self, src, in_off, with_consumed=False):
+        """The host-buffer form into a buffer of this call's own.  Its size is a guess first (four times the input): when the
+        planned layout does not fit, the call has written nothing and out_off[n] says what it takes (include/kcgpu.h), so the call
+        is made once more with exactly that — the usual input is walked twice, as a call with a known capacity is, never more than
+        three times."""
+        import numpy as np
+        ctx = self.ctx()
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        if len(src) == 0:
+            src = np.zeros(1, dtype=np.uint8)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = len(in_off) - 1
+        out_off, status, used = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint64)
+        fn = getattr(ctx.L, self._prefix)
+        cap = 4 * int(in_off[-1] - in_off[0]) + (64 << 10)
+        while True:
+            dst = np.empty(cap + 64, dtype=np.uint8)
+            rc = fn(ctx.h, self._o, src.ctypes.data, in_off.ctypes.data, n, dst.ctypes.data, cap, out_off.ctypes.data, status.ctypes.data, used.ctypes.data)
+            if rc != _lib.KC_ERR_DST_TOO_SMALL or int(out_off[n]) <= cap:
+                break
+            cap = int(out_off[n])
+        ctx.check(rc)
+        res = [self.error(status[i]) if status[i] else dst[int(out_off[i]):int(out_off[i + 1])].tobytes() for i in range(n)]
+        return (res, used[:n]) if with_consumed else res
+
+    def close(self):
+        c, self._ctx = self._ctx, None
+        if c is not None:
+            c.close()
+
+    def __del__(self):
+        try:
+            self.close()
+            if getattr(self, "_o", None):
+                _lib.load().kc_flate_ropts_free(self._o)
+                self._o = None
+        except Exception:
+            pass
+
+
+def InflateAll(src, in_off, dict=None, device=0):
+    """N x io.ReadAll(flate.NewReaderDict(input_i, dict)) in one batch.  src: numpy uint8 (host), the inputs concatenated; in_off:
+    uint64[n + 1].  Returns a list with, per input, its bytes or the InflateError that refused it."""
+    b = Batch("kc_flate_inflate", _ERRORS, dict=dict, device=device)
+    try:
+        return b.all_host(src, in_off)
+    finally:
+        b.close()
+
+
+def InflateBounds(src, in_off, dict=None, device=0):
+    """The sizing pass alone (kc_flate_inflate_bound): (uint64[n] exact decoded sizes, uint32[n] KC_FL_* status, uint64[n] consumed)."""
+    import numpy as np
+    b = Batch("kc_flate_inflate", _ERRORS, dict=dict, device=device)
+    try:
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        if len(src) == 0:
+            src = np.zeros(1, dtype=np.uint8)
+        return b.bounds(src.ctypes.data, in_off, False)
+    finally:
+        b.close()
+
+
+def InflateAllDevice(d_src_ptr, in_off, d_dst_ptr, dst_cap, dict=None, device=0, stream=None):
+    """Device-resident form (pointers are ints): returns (uint64[n + 1] offsets, uint32[n] status, uint64[n] consumed), host numpy.
+    A failed input's range is empty.  Raises KcError KC_ERR_DST_TOO_SMALL when the layout does not fit dst_cap (nothing is written)."""
+    b = Batch("kc_flate_inflate", _ERRORS, dict=dict, device=device, stream=stream)
+    try:
+        return b.inflate(d_src_ptr, in_off, d_dst_ptr, dst_cap, True)
+    finally:
+        b.close()
+
+
+class Reader:
+    """flate.NewReader / NewReaderDict (inflate.go:929-957) as a reader object: Read, WriteTo, Reset, Close.
+
+    The WHOLE input is read from r and decoded on the device on first use (one input is one wave's work; there is no
+    bounded-memory stream reader yet): Read and WriteTo then hand out the decoded bytes.  An input that fails raises on first use;
+    no byte of it is handed out."""
+
+    _prefix, _errors = "kc_flate_inflate", _ERRORS
+
+    def __init__(self, r, dict=None, device=0):
+        self._device = device
+        self.Reset(r, dict)
+
+    def Reset(self, r, dict=None):
+        """Resetter.Reset (inflate.go:68-75): read from r, with the preset dictionary dict, from now on."""
+        self._r, self._dict, self._out, self._at, self._err = r, dict, None, 0, None
+
+    def _options(self):
+        return {"dict": self._dict}
+
+    def _decode(self):
+        if self._out is None and self._err is None:
+            import numpy as np
+            data = self._r.read() if hasattr(self._r, "read") else bytes(self._r)
+            self._data = data
+            b = Batch(self._prefix, self._errors, device=self._device, **self._options())
+            try:
+                res, used = b.all_host(np.frombuffer(data, dtype=np.uint8), np.array([0, len(data)], dtype=np.uint64), with_consumed=True)
+            finally:
+                b.close()
+            self.consumed = int(used[0])
+            if isinstance(res[0], InflateError):
+                self._err = res[0]
+            else:
+                self._out = res[0]
+        if self._err is not None:
+            raise self._err
+
+    def Read(self, p):
+        """Fills p (a writable buffer) and returns the count; 0 at the end."""
+        self._decode()
+        m = memoryview(p).cast("B")
+        n = min(len(m), len(self._out) - self._at)
+        m[:n] = self._out[self._at:self._at + n]
+        self._at += n
+        return n
+
+    def WriteTo(self, w):
+        """Writes the rest of the decoded bytes to w and returns their count."""
+        self._decode()
+        n = len(self._out) - self._at
+        if n:
+            w.write(self._out[self._at:])
+        self._at = len(self._out)
+        return n
+
+    def Close(self):
+        self._out, self._err = b"", None
+        self._at = 0
+
+
+def NewReader(r, device=0):
+    """flate.NewReader(r)."""
+    return Reader(r, None, device=device)
+
+
+def NewReaderDict(r, dict, device=0):
+    """flate.NewReaderDict(r, dict): only the dictionary's last 32 KiB count."""
+    return Reader(r, dict, device=device)

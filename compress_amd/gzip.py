@@ -1,0 +1,123 @@
+"""compress/gzip's reader on the device: gzip files (RFC 1952), any number of members, inflated in batches of independent inputs
+(include/kcgpu.h kc_gzip_inflate*).  Headers, trailers, ISIZE and CRC-32 are checked on the device; the Header fields of the first
+member are parsed here, on the host.  There is no CPU fallback."""
+from . import flate
+from .flate import InflateError, CorruptInputError, ErrUnexpectedEOF  # noqa: F401
+
+
+class ErrHeader(InflateError):
+    """gzip.ErrHeader: "gzip: invalid header"."""
+
+    def __init__(self, status=flate.FL_HEADER):
+        super().__init__(status)
+
+
+class ErrChecksum(InflateError):
+    """gzip.ErrChecksum: "gzip: invalid checksum" — the CRC-32 or the ISIZE of a member."""
+
+    def __init__(self, status=flate.FL_CHECKSUM):
+        super().__init__(status)
+
+
+_ERRORS = dict(flate._ERRORS)
+_ERRORS.update({flate.FL_HEADER: ErrHeader, flate.FL_CHECKSUM: ErrChecksum})
+
+
+class Header:
+    """gzip.Header (gunzip.go:52-58) of a file's first member."""
+
+    def __init__(self):
+        self.Comment, self.Extra, self.ModTime, self.Name, self.OS = "", None, 0, "", 0
+
+
+def parse_header(data):
+    """The fields readHeader (gunzip.go:183-253) fills, from the front of data; ModTime in seconds since 1970.  None when the device
+    will refuse the header: validity is its verdict, this only extracts."""
+    d = bytes(data[:10])
+    if len(d) < 10 or d[0] != 0x1F or d[1] != 0x8B or d[2] != 8:
+        return None
+    h = Header()
+    flg = d[3]
+    h.ModTime = int.from_bytes(d[4:8], "little")
+    h.OS = d[9]
+    pos = 10
+    if flg & 4:
+        n = int.from_bytes(data[pos:pos + 2], "little")
+        h.Extra = bytes(data[pos + 2:pos + 2 + n])
+        pos += 2 + n
+    for bit, key in ((8, "Name"), (16, "Comment")):
+        if flg & bit:
+            end = bytes(data[pos:pos + 513]).find(b"\0")
+            if end < 0:
+                return None
+            setattr(h, key, bytes(data[pos:pos + end]).decode("latin-1"))
+            pos += end + 1
+    return h
+
+
+def GunzipAll(src, in_off, multistream=True, device=0):
+    """N x io.ReadAll(gzip.NewReader(input_i)) in one batch (host buffers): a list of bytes or the InflateError per input."""
+    b = flate.Batch("kc_gzip_inflate", _ERRORS, multistream=multistream, device=device)
+    try:
+        return b.all_host(src, in_off)
+    finally:
+        b.close()
+
+
+def GunzipBounds(src, in_off, multistream=True, device=0):
+    """The sizing pass alone (kc_gzip_inflate_bound): (sizes, status short of the CRC-32, consumed)."""
+    import numpy as np
+    b = flate.Batch("kc_gzip_inflate", _ERRORS, multistream=multistream, device=device)
+    try:
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        if len(src) == 0:
+            src = np.zeros(1, dtype=np.uint8)
+        return b.bounds(src.ctypes.data, in_off, False)
+    finally:
+        b.close()
+
+
+def GunzipAllDevice(d_src_ptr, in_off, d_dst_ptr, dst_cap, multistream=True, device=0, stream=None):
+    """Device-resident form: (uint64[n + 1] offsets, uint32[n] status, uint64[n] consumed).  A failed input's range is empty or
+    zero-filled."""
+    b = flate.Batch("kc_gzip_inflate", _ERRORS, multistream=multistream, device=device, stream=stream)
+    try:
+        return b.inflate(d_src_ptr, in_off, d_dst_ptr, dst_cap, True)
+    finally:
+        b.close()
+
+
+class Reader(flate.Reader):
+    """gzip.Reader (gunzip.go:74-124): Multistream, Read, WriteTo, Reset, Close and .Header of the first member.  Like flate.Reader
+    the whole input is read and decoded on the device on first use."""
+
+    _prefix, _errors = "kc_gzip_inflate", _ERRORS
+
+    def __init__(self, r, device=0):
+        self._multistream = True
+        super().__init__(r, None, device=device)
+
+    def Reset(self, r, dict=None):
+        """Reader.Reset (gunzip.go:105-124): read from r from now on; Multistream is on again."""
+        super().Reset(r, None)
+        self._multistream = True
+        self._header = None
+
+    def Multistream(self, ok):
+        """Reader.Multistream (gunzip.go:142-144)."""
+        self._multistream = bool(ok)
+
+    def _options(self):
+        return {"multistream": self._multistream}
+
+    @property
+    def Header(self):
+        self._decode()
+        if self._header is None:
+            self._header = parse_header(self._data)
+        return self._header
+
+
+def NewReader(r, device=0):
+    """gzip.NewReader(r)."""
+    return Reader(r, device=device)

@@ -604,6 +604,75 @@ uint64_t kc_s2_rstream_skip_left(const kc_s2_rstream* s);
 kc_status kc_s2_rstream_on_skippable(kc_s2_rstream* s, uint8_t id, kc_s2_skippable_fn fn, void* user);
 kc_status kc_s2_rstream_reset(kc_s2_rstream* s);
 void kc_s2_rstream_free(kc_s2_rstream* s);
+/* ---- flate.NewReader / gzip.NewReader over a batch of independent inputs (inflate) ----
+ * Raw DEFLATE (RFC 1951) and gzip (RFC 1952), whole inputs, ONE WAVE PER INPUT: zip members, gzip members, BGZF blocks, HTTP
+ * bodies, PNG IDAT runs.  No sizes are supplied: a sizing pass walks every input and yields its exact decoded size before any byte
+ * is written, the prefix sum of the sizes is the output layout, and a write pass decodes every input straight to its place.
+ * Options: kc_flate_ropts_default returns a new object with the reference's defaults (no dictionary, multistream on);
+ * kc_flate_ropts_dict == flate.NewReaderDict (flate/inflate.go:948-957): ONE preset dictionary per call, of which the last 32 KiB
+ * count (the window); it is read by the flate entry points only.  kc_flate_ropts_multistream == gzip.Reader.Multistream
+ * (gzip/gunzip.go:126-144), read by the gzip entry points only.  Both return 0, -1 on a null object. */
+typedef struct kc_flate_ropts kc_flate_ropts;
+kc_flate_ropts* kc_flate_ropts_default(void);
+void kc_flate_ropts_free(kc_flate_ropts* o);
+int kc_flate_ropts_dict(kc_flate_ropts* o, const uint8_t* bytes, uint64_t len);
+int kc_flate_ropts_multistream(kc_flate_ropts* o, int b);
+/* per-input status of the inflate entry points */
+enum {
+    KC_FL_OK = 0,
+    KC_FL_CORRUPT = 1,        /* flate.CorruptInputError, whatever its offset */
+    KC_FL_EOF = 2,            /* io.ErrUnexpectedEOF; also a gzip input of zero bytes, for which gzip.NewReader returns io.EOF */
+    KC_FL_HEADER = 3,         /* gzip.ErrHeader */
+    KC_FL_CHECKSUM = 4,       /* gzip.ErrChecksum: CRC-32 or ISIZE */
+    KC_FL_SIZE_EXCEEDED = 5   /* a limit of this library, the one deviation from the reference: an input that decodes to more than 1 GiB,
+                                 or (host-buffer forms) one whose input bytes plus decoded bytes are above a quarter of the context's
+                                 scratch budget (KC_OPT_MAX_SCRATCH_MIB, and 85 % of what is free) */
+};
+/* kc_flate_inflate[_dev] == io.ReadAll(flate.NewReaderDict(bytes.NewReader(input), dict)) for every input (flate/inflate.go:352-395
+ * nextBlock, :464-597 readHuffman, :600-670 dataBlock / copyData, :116-176 huffmanDecoder.init, :740-783 huffSym;
+ * flate/inflate_gen.go:45-270 the block body).  src: the inputs, concatenated; in_off: n + 1 ascending offsets; dst / dst_cap: the
+ * output; out_off[n + 1], status[n], consumed[n] (may be NULL): host arrays in both forms.  The _dev form takes device pointers
+ * for src and dst.
+ * Output: out_off is dense — input i owns dst[out_off[i], out_off[i + 1]), its exact decoded size.  An input that fails gets an
+ * empty range, or (gzip) the range of its members in front of the failure, zero-filled: in neither case is a byte decoded from a
+ * failed input left in dst, and its neighbours are untouched.  KC_ERR_DST_TOO_SMALL when out_off[n] > dst_cap: nothing is written,
+ * and out_off holds the planned layout — out_off[n] is the capacity to come back with.
+ * consumed[i]: the input bytes up to and including the byte that holds the last bit of the final block — the reference never reads
+ * past it from a ByteReader (inflate.go:582-594); bytes behind it are ignored.  0 for an input that failed.
+ * The reference's own quirk is kept: an input that ends inside the extra bits of a length or distance, or inside a fixed block's
+ * five distance bits, ends with the raw io.EOF (inflate_gen.go:114-122, 142-151, 210-219), so ReadAll returns what was decoded
+ * WITHOUT an error: KC_FL_OK.  (gzip then misses its trailer: KC_FL_EOF.)
+ * kc_flate_inflate_bound[_dev]: the sizing pass alone — bound[i] = the exact decoded size of every input that stands, status[i] its
+ * verdict, consumed[i] as above.
+ * The host-buffer forms stage the inputs in groups cut between inputs: a group's input bytes (first sweep, the sizes) and its input
+ * bytes plus decoded bytes (second sweep, the write) stay within a QUARTER of the context's scratch budget — the smaller of
+ * KC_OPT_MAX_SCRATCH_MIB and 85 % of the free device memory.  An input whose bytes, or whose bytes plus decoded bytes, are above
+ * that quarter alone gets KC_FL_SIZE_EXCEEDED.  They do not use the rolling host pipeline. */
+kc_status kc_flate_inflate_dev(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint8_t* d_dst,
+                               uint64_t dst_cap, uint64_t* out_off, uint32_t* status, uint64_t* consumed);
+kc_status kc_flate_inflate(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst,
+                           uint64_t dst_cap, uint64_t* out_off, uint32_t* status, uint64_t* consumed);
+kc_status kc_flate_inflate_bound_dev(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n,
+                                     uint64_t* bound, uint32_t* status, uint64_t* consumed);
+kc_status kc_flate_inflate_bound(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n,
+                                 uint64_t* bound, uint32_t* status, uint64_t* consumed);
+/* kc_gzip_inflate[_dev] == io.ReadAll(gzip.NewReader(bytes.NewReader(input))) for every input, under Multistream (gzip/gunzip.go:94-124
+ * NewReader / Reset, :183-253 readHeader, :255-295 Read: the trailer, the next member).  Arguments and output as above.
+ * consumed[i] runs through the last trailer read; with Multistream off, what lies behind it is the next member's header.
+ * The sizing pass walks headers, streams, trailers and the ISIZE compare, member after member; the write pass computes the CRC-32 of
+ * every member's bytes and compares it with the trailer (KC_FL_CHECKSUM: the planned range is zero-filled).  An input that fails
+ * behind complete members keeps their range, zero-filled.  kc_gzip_inflate_bound[_dev]: the sizing pass alone — the first error short
+ * of the CRC-32; bound[i] of a failed input is the size of the range it would keep.  The Header fields are parsed by the caller
+ * (compress_amd/gzip.py).  ISIZE is compared modulo 2^32 as in the reference. */
+kc_status kc_gzip_inflate_dev(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint8_t* d_dst,
+                              uint64_t dst_cap, uint64_t* out_off, uint32_t* status, uint64_t* consumed);
+kc_status kc_gzip_inflate(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst,
+                          uint64_t dst_cap, uint64_t* out_off, uint32_t* status, uint64_t* consumed);
+kc_status kc_gzip_inflate_bound_dev(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n,
+                                    uint64_t* bound, uint32_t* status, uint64_t* consumed);
+kc_status kc_gzip_inflate_bound(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n,
+                                uint64_t* bound, uint32_t* status, uint64_t* consumed);
+
 /* Single-block form with the WriterCustomEncoder contract (s2/writer.go:1053-1064): no varint header;
  * returns bytes used, 0 = incompressible (store raw), <0 = fall back to the built-in encoder.
  * "The function should expect to be called concurrently" (writer.go:1058; s2.Writer calls it from one goroutine per block,

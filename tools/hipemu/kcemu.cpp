@@ -27,6 +27,7 @@
 #include "../../compress_amd/csrc/kc_s2_index.cpp"   // (host code: s2.Index, exported from this library as from the product)
 #include "../../compress_amd/csrc/kc_s2_rstream.hip"
 #include "../../compress_amd/csrc/kc_s2rstream_host.h"
+#include "../../compress_amd/csrc/kc_flate_inflate.hip"
 
 // s2.Reader / s2.Decode over n inputs on the emulator: the plan kernel (both passes), the decode kernel with its CRC, the verdict per
 // input (first failing chunk in stream order, else the plan's error) and the zero-fill of the failed ranges — kc_s2_dec_api.cpp's
@@ -59,6 +60,26 @@ static int kcemu_s2_decode(const KcS2PlanParams& P0, int ignore_crc, uint8_t* ds
         status[i] = v;
         if (v && bd[i]) memset(dst + out_off[i], 0, (size_t)bd[i]);
     }
+    return 0;
+}
+
+// flate.NewReader / gzip.NewReader over n inputs on the emulator: the sizing pass, the exclusive scan of its sizes, the write pass with
+// its CRC-32 and zero-fill — kc_flate_api.cpp's sequence as one batch in plain memory.  Returns 0, -2 when dst_cap is too small
+// (nothing written).
+static int kcemu_flate(KcFlateParams P, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* bound, uint32_t* status, uint64_t* consumed) {
+    const uint32_t n = P.n;
+    std::vector<uint64_t> size(n + 1, 0), used(n + 1, 0);
+    std::vector<uint32_t> st(n + 1, 0xA7A7A7A7u), mem(n + 1, 0), wst(n + 1, 0xA7A7A7A7u);
+    P.size = size.data(); P.status = st.data(); P.consumed = used.data(); P.members = mem.data();
+    kc_launch_flate_size(P, nullptr);
+    out_off[0] = 0;
+    for (uint32_t i = 0; i < n; i++) { out_off[i + 1] = out_off[i] + size[i]; bound[i] = size[i]; status[i] = st[i]; if (consumed) consumed[i] = used[i]; }
+    if (!dst) return 0;  // the bound alone
+    if (out_off[n] > dst_cap) return -2;
+    P.out0 = out_off; P.dst = dst; P.wstatus = wst.data();
+    kc_launch_flate_write(P, nullptr);
+    for (uint32_t i = 0; i < n; i++)
+        if (mem[i]) { status[i] = wst[i]; if (wst[i] && consumed) consumed[i] = 0; }
     return 0;
 }
 
@@ -285,6 +306,24 @@ int kcemu_s2_decode_streams(const uint8_t* src, const uint64_t* in_off, uint32_t
     memset(&P, 0, sizeof(P));
     P.src = src; P.in_off = in_off; P.n = n; P.max_block = max_block; P.max_buf = max_buf; P.ignore_id = ignore_id;
     return kcemu_s2_decode(P, ignore_crc, dst, dst_cap, out_off, bound, status);
+}
+
+// N x io.ReadAll(flate.NewReaderDict(input, dict)); dst null: the sizing pass alone
+int kcemu_flate_inflate(const uint8_t* src, const uint64_t* in_off, uint32_t n, const uint8_t* dict, uint32_t dict_len, uint8_t* dst, uint64_t dst_cap,
+                        uint64_t* out_off, uint64_t* bound, uint32_t* status, uint64_t* consumed) {
+    KcFlateParams P;
+    memset(&P, 0, sizeof(P));
+    if (dict_len > 32768) { dict += dict_len - 32768; dict_len = 32768; }
+    P.src = src; P.in_off = in_off; P.n = n; P.dict = dict; P.dict_len = dict_len;
+    return kcemu_flate(P, dst, dst_cap, out_off, bound, status, consumed);
+}
+// N x io.ReadAll(gzip.NewReader(input)) under Multistream(multistream)
+int kcemu_gzip_inflate(const uint8_t* src, const uint64_t* in_off, uint32_t n, int multistream, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off,
+                       uint64_t* bound, uint32_t* status, uint64_t* consumed) {
+    KcFlateParams P;
+    memset(&P, 0, sizeof(P));
+    P.src = src; P.in_off = in_off; P.n = n; P.gzip = 1; P.multistream = multistream != 0;
+    return kcemu_flate(P, dst, dst_cap, out_off, bound, status, consumed);
 }
 
 // s2.ReadSeeker.ReadAt over m requests on the emulator: Index.Find per request, the ranged plan (both passes), the clipped decode,

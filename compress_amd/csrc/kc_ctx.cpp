@@ -307,21 +307,17 @@ static void ctx_free_scratch(kc_ctx* c) {
         b->p = nullptr;
         b->cap = 0;
     }
-    for (DevBuf& b : c->zd) {  // DecodeAll (kc_zstd_dec_api.cpp)
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr;
-        b.cap = 0;
-    }
-    for (DevBuf& b : c->s2d) {  // s2.Reader (kc_s2_dec_api.cpp)
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr;
-        b.cap = 0;
-    }
-    for (DevBuf& b : c->fl) {  // flate / gzip readers (kc_flate_api.cpp)
-        if (b.p) (void)hipFree(b.p);
-        b.p = nullptr;
-        b.cap = 0;
-    }
+    auto free_all = [](DevBuf* b, size_t n) {
+        for (; n; b++, n--) {
+            if (b->p) (void)hipFree(b->p);
+            b->p = nullptr;
+            b->cap = 0;
+        }
+    };
+    free_all(c->zd, sizeof(c->zd) / sizeof(DevBuf));    // DecodeAll (kc_zstd_dec_api.cpp)
+    free_all(c->s2d, sizeof(c->s2d) / sizeof(DevBuf));  // s2.Reader (kc_s2_dec_api.cpp)
+    free_all(c->s2r, sizeof(c->s2r) / sizeof(DevBuf));  // ranged reads (kc_s2_ranges_api.cpp)
+    free_all(c->fl, sizeof(c->fl) / sizeof(DevBuf));    // flate / gzip readers (kc_flate_api.cpp)
     // what the context remembered about the freed buffers' contents
     c->predef_ready = false;
     c->tab_owner = 0;

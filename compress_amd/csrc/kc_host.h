@@ -1,8 +1,12 @@
 #pragma once
 // kc_host.h — internal header of the host side of the C ABI (include/kcgpu.h): the context, its scratch buffers and the batch
 // records shared by the translation units kc_ctx.cpp (options, context), kc_batch.cpp (the zstd device pipeline), kc_zstd_host.cpp
-// (host-buffer entry points), kc_jobs.cpp (WithConcurrentBlocks), kc_s2_api.cpp (S2), kc_zstd_dec_api.cpp (DecodeAll), kc_zstd_dstream_api.cpp (the stream reader), kc_s2_dec_api.cpp (s2.Reader), kc_flate_api.cpp (flate / gzip readers) and kc_hook.cpp
-// (the WriterCustomEncoder hook).
+// (host-buffer entry points), kc_jobs.cpp (WithConcurrentBlocks), kc_s2_api.cpp (S2), kc_hook.cpp (the WriterCustomEncoder hook) and the
+// decoders' entry points: kc_zstd_dec_api.cpp (DecodeAll), kc_s2_dec_api.cpp (s2.Reader / s2.Decode), kc_s2_ranges_api.cpp (ReadAt),
+// kc_flate_api.cpp (flate / gzip readers), kc_zstd_dstream_api.cpp and kc_s2_rstream_api.cpp (the stream readers).  The decoders'
+// host sequences themselves are not here: they live in headers over a small device interface (kc_decdev_host.h; kc_zdec_host.h,
+// kc_s2dec_host.h, kc_s2ranges_host.h, kc_flate_host.h, kc_zdstream_host.h, kc_s2rstream_host.h) that know neither HIP nor the
+// context, and the entry points hand them HipDevice (kc_decdev_hip.h).
 // Not installed: the boundary is include/kcgpu.h.
 // There is deliberately NO CPU fallback in this library: when the device path cannot serve a
 // request it returns KC_ERR_UNSUPPORTED / KC_ERR_NO_DEVICE and the caller (the Go shim)
@@ -25,6 +29,7 @@
 
 #include "../../include/kcgpu.h"
 #include "kc_kernels.h"
+#include "kc_zdec_host.h"
 
 
 namespace kci {
@@ -173,10 +178,11 @@ struct kc_ctx {
     const uint8_t* job_tables = nullptr;    // host or null: the units' tables primed from their prefixes (ResetPrefix), device entry format
     bool job_primed = false;                // the units' tables start primed from their prefixes: by kc_zstd_prime_kernel, or from job_tables
     DevBuf d_job_hist, d_job_flags, rawdef, unit_raw;
-    DevBuf zd[20];                       // zstd.Decoder.DecodeAll (kc_zstd_dec_api.cpp): plan, frame records, staging, literal scratch
-    DevBuf s2d[13];                      // s2.Reader / s2.Decode (kc_s2_dec_api.cpp): plan results, chunk records, chunk verdicts; from [8] on the
-                                         // ranged reads (kc_s2_ranges_api.cpp): requests, their plans, chunk records, verdicts, clip slots
-    DevBuf fl[8];                        // flate / gzip inflate (kc_flate_api.cpp): offsets, the sizing pass's results, the write pass's verdicts, the dictionary
+    // the batch decoders' buffers, one slot per entry of the sequence's enum (each entry point file asserts the size)
+    DevBuf zd[20];                       // zstd.Decoder.DecodeAll (ZD_*, kc_zdec_host.h): plan, frame records, staging, literal scratch
+    DevBuf s2d[8];                       // s2.Reader / s2.Decode (SD_*, kc_s2dec_host.h): plan results, chunk records, chunk verdicts
+    DevBuf s2r[5];                       // ranged reads (SR_*, kc_s2ranges_host.h): requests, their plans, chunk records, verdicts, clip slots
+    DevBuf fl[8];                        // flate / gzip inflate (FL_*, kc_flate_host.h): offsets, the sizing pass's results, the write pass's verdicts, the dictionary
     DevBuf unit_done, probe_rel;         // no-match pre-scan (kc_zstd_prescan.hip): per-unit verdicts; the probe positions of one block
     int probe_bs = 0;                    // block size probe_rel was built for
     uint32_t probe_n = 0;
@@ -209,15 +215,10 @@ struct kc_s2_ropts {
     int ignore_crc = 0;
     int ignore_id = 0;
 };
+inline uint32_t max_buf_of(uint32_t max_block) { return (uint32_t)kc_s2_max_encoded_len((int64_t)max_block) + 4u; }  // Reader.maxBufSize (s2/reader.go:42)
 
 // the decoderOptions behind kc_zstd_dopts_* (kc_zstd_dec_api.cpp), read by DecodeAll and by the stream reader (kc_zstd_dstream_api.cpp)
-struct kc_zstd_dopts {
-    uint64_t max_memory = (uint64_t)64 << 30;   // decoderOptions.maxDecodedSize
-    uint64_t max_window = (uint64_t)1 << 29;    // decoderOptions.maxWindowSize (MaxWindowSize)
-    int ignore_checksum = 0;
-    std::vector<KcZdDict> dicts;                // content_off = the dictionary's place in `arena`
-    std::vector<uint8_t> arena;                 // the dictionaries' contents, each 16-byte aligned
-};
+struct kc_zstd_dopts : KcZdOpts {};
 
 namespace kci {
 

@@ -1,44 +1,16 @@
 // kc_s2_rstream_api.cpp — s2.NewReader(r).Read / Skip / ReadByte on the device: the entry points kc_s2_rstream_new / _feed / _skip /
 // _skip_left / _on_skippable / _reset / _free of include/kcgpu.h.  The state machine is kc_s2rstream_host.h's; this file gives it the
-// device: buffers of the stream's own (one window of staged compressed bytes and its decoded bytes, the chunk records, the
-// verdicts), copies and the kernel of kc_s2_rstream.hip on the context's stream.
-#include "kc_host.h"
+// device: HipDevice (kc_decdev_hip.h) with buffers of the stream's own (one window of staged compressed bytes and its decoded bytes,
+// the chunk records, the verdicts) on the context's stream.
+#include "kc_decdev_hip.h"
 #include "kc_s2rstream_host.h"
 
-namespace {
-
-struct HipDevice : KcS2rDevice {
-    kc_ctx* c = nullptr;
-    DevBuf buf[B_N];
-    int reserve(int which, size_t bytes, void** p) override {
-        const kc_status s = ensure(c, buf[which], bytes ? bytes : 1);
-        *p = buf[which].p;
-        return s;
-    }
-    int h2d(void* d, const void* h, size_t n) override {
-        if (n) HIPCHK(c, hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, c->stream));
-        return KC_OK;
-    }
-    int d2h(void* h, const void* d, size_t n) override {
-        if (n) HIPCHK(c, hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, c->stream));
-        return KC_OK;
-    }
-    void launch(const KcS2RstreamParams& P) override { kc_launch_s2_rstream(P, c->stream); }
-    int sync() override {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipGetLastError());
-        return KC_OK;
-    }
-    ~HipDevice() override {
-        for (DevBuf& b : buf) if (b.p) (void)hipFree(b.p);
-    }
-};
-
-}  // namespace
+static_assert(RS_N <= HipDevice::OWN_N, "HipDevice holds every buffer of the stream");
 
 struct kc_s2_rstream {
     HipDevice dev;
     KcS2rStream s;
+    explicit kc_s2_rstream(kc_ctx* c) : dev(c) { s.dev = &dev; }
 };
 
 extern "C" {
@@ -46,11 +18,9 @@ extern "C" {
 kc_s2_rstream* kc_s2_rstream_new(kc_ctx* c, const kc_s2_ropts* o) {  // NewReader (s2/reader.go:31): a copy of the options
     if (!c || !o) return nullptr;
     try {
-        kc_s2_rstream* z = new kc_s2_rstream();
-        z->dev.c = c;
-        z->s.dev = &z->dev;
+        kc_s2_rstream* z = new kc_s2_rstream(c);
         z->s.o.max_block = o->max_block;
-        z->s.o.max_buf = (uint32_t)kc_s2_max_encoded_len((int64_t)o->max_block) + 4u;  // Reader.maxBufSize (s2/reader.go:42)
+        z->s.o.max_buf = max_buf_of(o->max_block);
         z->s.o.ignore_crc = o->ignore_crc;
         z->s.o.ignore_id = o->ignore_id;
         z->s.o.chunks = (uint32_t)c->cfg.s2_rstream_chunks;

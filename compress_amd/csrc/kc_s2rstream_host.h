@@ -17,20 +17,11 @@
 #include <string.h>
 #include <vector>
 #include "../../include/kcgpu.h"
-#include "kc_kernels.h"
+#include "kc_decdev_host.h"
 #include "kc_s2_plan_dev.h"
 
-// What the state machine needs of a device.  Copies and the launch are ordered; sync() waits for all of them.  The source of an h2d
-// and the target of a d2h stay untouched until the next sync().
-struct KcS2rDevice {
-    enum { B_IN, B_RECS, B_STAT, B_OUT, B_N };
-    virtual int reserve(int which, size_t bytes, void** p) = 0;  // at least `bytes`; a buffer that grows loses its contents
-    virtual int h2d(void* d, const void* h, size_t n) = 0;
-    virtual int d2h(void* h, const void* d, size_t n) = 0;
-    virtual void launch(const KcS2RstreamParams& P) = 0;
-    virtual int sync() = 0;
-    virtual ~KcS2rDevice() {}
-};
+// The stream's buffers on its device (kc_decdev_host.h).
+enum { RS_IN, RS_RECS, RS_STAT, RS_OUT, RS_N };
 
 struct KcS2rOpts {
     uint32_t max_block = 4u << 20;
@@ -41,7 +32,7 @@ struct KcS2rOpts {
 
 struct KcS2rStream {
     enum { WALK, PAYLOAD, FAILED, DONE };
-    KcS2rDevice* dev = nullptr;
+    KcDecDevice* dev = nullptr;
     KcS2rOpts o;
     int state = WALK;
     uint32_t fail = 0;
@@ -78,15 +69,15 @@ struct KcS2rStream {
         int s;
         *cls = 0;
         *produced = 0;
-        if ((s = dev->reserve(KcS2rDevice::B_IN, (size_t)in_len, &d_in)) || (s = dev->reserve(KcS2rDevice::B_RECS, (size_t)count * sizeof(KcS2WChunk), &d_recs)) ||
-            (s = dev->reserve(KcS2rDevice::B_STAT, (size_t)count * 4, &d_stat)) || (s = dev->reserve(KcS2rDevice::B_OUT, (size_t)out_len, &d_out)))  // (the kernel bounds every access exactly: no slack)
+        if ((s = dev->reserve(RS_IN, (size_t)in_len, &d_in)) || (s = dev->reserve(RS_RECS, (size_t)count * sizeof(KcS2WChunk), &d_recs)) ||
+            (s = dev->reserve(RS_STAT, (size_t)count * 4, &d_stat)) || (s = dev->reserve(RS_OUT, (size_t)out_len, &d_out)))  // (the kernel bounds every access exactly: no slack)
             return s;
         if ((s = dev->h2d(d_in, in, (size_t)in_len)) || (s = dev->h2d(d_recs, recs.data(), (size_t)count * sizeof(KcS2WChunk)))) return s;
         KcS2RstreamParams P;
         memset(&P, 0, sizeof(P));
         P.in = (const uint8_t*)d_in; P.in_len = in_len; P.chunks = (const KcS2WChunk*)d_recs; P.n_chunks = count; P.out = (uint8_t*)d_out;
         P.out_len = out_len; P.ignore_crc = o.ignore_crc; P.status = (uint32_t*)d_stat;
-        dev->launch(P);
+        kc_launch_s2_rstream(P, dev->stream);
         stat.assign(count, 0);
         if ((s = dev->d2h(stat.data(), d_stat, (size_t)count * 4)) || (s = dev->sync())) return s;
         uint64_t good = 0;  // decoded bytes in front of the first failing chunk

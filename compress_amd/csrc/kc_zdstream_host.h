@@ -24,35 +24,19 @@
 #include <string.h>
 #include <vector>
 #include "../../include/kcgpu.h"
-#include "kc_kernels.h"
+#include "kc_zdec_host.h"
 #include "kc_zblock_dev.h"
 
-// What the state machine needs of a device.  Copies and launches are ordered; sync() waits for all of them.  The source of an h2d
-// and the target of a d2h stay untouched until the next sync().
-struct KcZsDevice {
-    enum { B_IN, B_RECS, B_LITS, B_SEQS, B_WTS, B_STAT, B_TAB, B_HASH, B_HIST0, B_HIST1, B_DICT, B_N };
-    virtual int reserve(int which, size_t bytes, void** p) = 0;  // at least `bytes`; a buffer that grows loses its contents
-    virtual int h2d(void* d, const void* h, size_t n) = 0;
-    virtual int d2h(void* h, const void* d, size_t n) = 0;
-    virtual int d2d(void* d, const void* s, size_t n) = 0;
-    virtual void entropy(const KcZsEntropyParams& P) = 0;
-    virtual void execute(const KcZsExecParams& P) = 0;
-    virtual void hash(const KcZsHashParams& P) = 0;
-    virtual int sync() = 0;
-    virtual ~KcZsDevice() {}
-};
+// The stream's buffers on its device (kc_decdev_host.h).
+enum { ZS_IN, ZS_RECS, ZS_LITS, ZS_SEQS, ZS_WTS, ZS_STAT, ZS_TAB, ZS_HASH, ZS_HIST0, ZS_HIST1, ZS_DICT, ZS_N };
 
-struct KcZsOpts {
-    uint64_t max_memory = (uint64_t)64 << 30, max_window = (uint64_t)1 << 29;
-    int ignore_checksum = 0;
+struct KcZsOpts : KcZdOpts {
     uint32_t blocks = 512;               // blocks per launch (KC_OPT_DSTREAM_BLOCKS)
-    std::vector<KcZdDict> dicts;         // content_off = the dictionary's place in `arena`
-    std::vector<uint8_t> arena;
 };
 
 struct KcZsStream {
     enum { BETWEEN, SKIP, BLOCKS, CHECKSUM, FAILED, DONE };
-    KcZsDevice* dev = nullptr;
+    KcDecDevice* dev = nullptr;
     KcZsOpts o;
     int state = BETWEEN;
     uint32_t fail = 0;
@@ -180,10 +164,10 @@ struct KcZsStream {
         for (int k = 0; k < 4; k++) if (last_def[k] != KC_ZS_CARRIED) { recs[last_def[k]].def |= 1u << k; def_mask |= 1u << k; }
         // ---- device buffers ----
         void *d_in, *d_recs, *d_lits, *d_seqs, *d_wts, *d_stat, *d_tab, *d_hash, *d_dict = nullptr;
-        if ((s = dev->reserve(KcZsDevice::B_IN, (size_t)in_len + 64, &d_in)) || (s = dev->reserve(KcZsDevice::B_RECS, (size_t)count * sizeof(KcZsBlock), &d_recs)) ||
-            (s = dev->reserve(KcZsDevice::B_LITS, (size_t)lits + 64, &d_lits)) || (s = dev->reserve(KcZsDevice::B_SEQS, (size_t)seqs * 4 + 64, &d_seqs)) ||
-            (s = dev->reserve(KcZsDevice::B_WTS, (size_t)wts + 64, &d_wts)) || (s = dev->reserve(KcZsDevice::B_STAT, 16 + (size_t)count * 12, &d_stat)) ||
-            (s = dev->reserve(KcZsDevice::B_TAB, 2 * sizeof(KcZsTables), &d_tab)) || (s = dev->reserve(KcZsDevice::B_HASH, sizeof(KcZsHash), &d_hash)))
+        if ((s = dev->reserve(ZS_IN, (size_t)in_len + 64, &d_in)) || (s = dev->reserve(ZS_RECS, (size_t)count * sizeof(KcZsBlock), &d_recs)) ||
+            (s = dev->reserve(ZS_LITS, (size_t)lits + 64, &d_lits)) || (s = dev->reserve(ZS_SEQS, (size_t)seqs * 4 + 64, &d_seqs)) ||
+            (s = dev->reserve(ZS_WTS, (size_t)wts + 64, &d_wts)) || (s = dev->reserve(ZS_STAT, 16 + (size_t)count * 12, &d_stat)) ||
+            (s = dev->reserve(ZS_TAB, 2 * sizeof(KcZsTables), &d_tab)) || (s = dev->reserve(ZS_HASH, sizeof(KcZsHash), &d_hash)))
             return s;
         KcZsTables* tabs = (KcZsTables*)d_tab;
         if (fresh) {  // the frame's first launch: no tables, or the dictionary's; its offset history; a new checksum; an empty history
@@ -207,7 +191,7 @@ struct KcZsStream {
                 dict_live = D.content_len != 0;
                 if (dict_live && dict_loaded != dict) {
                     dict_loaded = 0;
-                    if ((s = dev->reserve(KcZsDevice::B_DICT, (size_t)D.content_len + 64, &d_dict)) ||
+                    if ((s = dev->reserve(ZS_DICT, (size_t)D.content_len + 64, &d_dict)) ||
                         (s = dev->h2d(d_dict, o.arena.data() + D.content_off, D.content_len)))
                         return s;
                     dict_loaded = dict;
@@ -220,7 +204,7 @@ struct KcZsStream {
             if ((s = dev->h2d(&tabs[cur], &tab0, sizeof(tab0))) || (s = dev->h2d(d_hash, &hash0, sizeof(hash0)))) return s;
         }
         if (dict_live) {
-            if ((s = dev->reserve(KcZsDevice::B_DICT, (size_t)o.dicts[dict - 1].content_len + 64, &d_dict))) return s;
+            if ((s = dev->reserve(ZS_DICT, (size_t)o.dicts[dict - 1].content_len + 64, &d_dict))) return s;
         }
         // ---- the history buffer: up to `window` bytes of what came before, then room for this launch ----
         if (kept + need > hist_cap[sel]) {
@@ -228,12 +212,12 @@ struct KcZsStream {
             const int other = sel ^ 1;
             const uint64_t want = (keep > window ? keep : window) + need;
             if (keep == 0 && hist_cap[sel] == 0) {  // (nothing to move)
-                if ((s = dev->reserve(KcZsDevice::B_HIST0 + sel, (size_t)(need + 64), &hist[sel]))) return s;
+                if ((s = dev->reserve(ZS_HIST0 + sel, (size_t)(need + 64), &hist[sel]))) return s;
                 hist_cap[sel] = need;
             } else {
                 // the slide goes into the second buffer: source and destination never overlap
                 if (hist_cap[other] < keep + need) {
-                    if ((s = dev->reserve(KcZsDevice::B_HIST0 + other, (size_t)(want + 64), &hist[other]))) return s;
+                    if ((s = dev->reserve(ZS_HIST0 + other, (size_t)(want + 64), &hist[other]))) return s;
                     hist_cap[other] = want;
                 }
                 if (keep && (s = dev->d2d(hist[other], (const uint8_t*)hist[sel] + (kept - keep), (size_t)keep))) return s;
@@ -253,7 +237,7 @@ struct KcZsStream {
         E.in = (const uint8_t*)d_in; E.in_len = in_len; E.blocks = (const KcZsBlock*)d_recs; E.n_blocks = count; E.window = window;
         E.lits = (uint8_t*)d_lits; E.lits_len = lits; E.seqs = (uint32_t*)d_seqs; E.seqs_len = seqs; E.wts = (uint8_t*)d_wts;
         E.cur = &tabs[cur]; E.next = &tabs[cur ^ 1]; E.status = d_est;
-        dev->entropy(E);
+        kc_launch_zstd_dstream_entropy(E, dev->stream);
         KcZsExecParams X;
         memset(&X, 0, sizeof(X));
         X.in = E.in; X.blocks = E.blocks; X.n_blocks = count; X.window = window; X.lits = E.lits; X.seqs = E.seqs; X.estatus = d_est;
@@ -261,13 +245,13 @@ struct KcZsStream {
         X.dict = dict_live ? (const uint8_t*)d_dict : nullptr;
         X.dict_len = dict_live ? o.dicts[dict - 1].content_len : 0;
         X.def_mask = def_mask; X.cur = E.cur; X.next = E.next; X.out_size = d_osz; X.status = d_xst; X.result = d_result;
-        dev->execute(X);
+        kc_launch_zstd_dstream_execute(X, dev->stream);
         const bool hashing = checksum && !o.ignore_checksum;
         if (hashing) {
             KcZsHashParams Hh;
             memset(&Hh, 0, sizeof(Hh));
             Hh.hist = X.hist; Hh.start = kept; Hh.result = d_result; Hh.h = (KcZsHash*)d_hash; Hh.final = has_last ? 1 : 0;
-            dev->hash(Hh);
+            kc_launch_xxh64_stream(Hh, dev->stream);
         }
         stat.assign((size_t)count * 2, 0);
         if ((s = dev->d2h(result, d_result, 16)) || (s = dev->d2h(stat.data(), d_xst, (size_t)count * 8))) return s;

@@ -4,6 +4,7 @@ Test infrastructure only.  The same .hip sources the product compiles with hipcc
 tools/hipemu/hip/hip_runtime.h, which runs every lane of a wave as a fiber and every cross-lane operation as a
 rendezvous; lanes run maximally out of lockstep in between, so an unfenced exchange through LDS shows up as a wrong
 result.  This is how the device algorithms are checked against the oracle without a GPU (tests/test_emu_lds.py)."""
+import contextlib
 import ctypes as C
 import functools
 import os
@@ -57,6 +58,33 @@ def lib():
             _L.kcemu_zfast_parse.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_int]
     return _L
+
+
+@contextlib.contextmanager
+def scratch_budget(nbytes):
+    """The batch decoders' sequences cut their batches to `nbytes` of device scratch inside the block (0: unlimited, the default)."""
+    L = lib()
+    L.kcemu_set_scratch_budget.restype = None
+    L.kcemu_set_scratch_budget.argtypes = [C.c_uint64]
+    L.kcemu_set_scratch_budget(nbytes)
+    try:
+        yield
+    finally:
+        L.kcemu_set_scratch_budget(0)
+
+
+def last_batches():
+    """Device batches the last batch decoder call was cut into."""
+    L = lib()
+    L.kcemu_last_batches.restype = C.c_int
+    return L.kcemu_last_batches()
+
+
+def last_max_need():
+    """The largest single input's scratch in the last batch decoder call, 1/8 allowance included: the least budget that refuses none."""
+    L = lib()
+    L.kcemu_last_max_need.restype = C.c_uint64
+    return L.kcemu_last_max_need()
 
 
 PROCS = int(os.environ.get("KC_EMU_PROCS", str(min(8, os.cpu_count() or 1))))

@@ -84,6 +84,21 @@ def test_directed_cases(emu):
     run_cases(emu, cases)
 
 
+def test_budget_changes_nothing(emu):
+    """The directed cases under a scratch budget of one byte: the device form of inflate keeps no scratch that grows with its inputs'
+    bytes, so it has no cut to make and no input to refuse — every batch is one device batch, whatever the budget, with the same
+    bytes, layout, statuses, consumed and bounds.  (The cuts of the inflate entry points are the host-buffer form's two sweeps.)"""
+    for fmt, zdict, ms, cs in FC.batches(FC.cases()):
+        inputs = [c.data for c in cs]
+        one = run_batch(emu, inputs, fmt, zdict, ms)
+        assert emu_lib.last_batches() == 1
+        with emu_lib.scratch_budget(1):
+            cut = run_batch(emu, inputs, fmt, zdict, ms)
+            assert emu_lib.last_batches() == 1
+        assert cut == one
+        judge(cs, cut)
+
+
 @emu_lib._fanned(min_bytes=1)
 def _emu_many(items, fmt):
     """Independent inputs of one format in forked children, a share each (wall-clock time only)."""

@@ -165,3 +165,23 @@ def test_refusals_between_good_neighbours(G):
     total = int(res.out_off[-1])
     short = run(inputs, cap=total - 1)  # (run() checks that dst is untouched)
     assert short.rc == K.DST_TOO_SMALL
+
+
+def test_budget_cuts_change_nothing(G):
+    """The batch of refusals between good neighbours, with the first-error streams behind it, as one device batch and again under the
+    least scratch budget the largest input fits alone (its chunk records plus the 1/8 allowance, as the sequence reports it): at
+    least three batches; the same bytes, layout, bounds and statuses.  s2.Reader's device form never refuses an input for size."""
+    items = K.item1_streams(G)
+    bad = [m for m in K.mutations([s for _, s, _ in items[:8]]) if K.judge_stream(G, m, 1 << 20)[0] == "err"][:len(items)]
+    inputs = [x for pair in zip([s for _, s, _ in items], bad) for x in pair] + [s for _, s, _ in K.first_error_cases(G)]
+    one = run(inputs)
+    assert one.rc == 0 and emu_lib.last_batches() == 1
+    need = emu_lib.last_max_need()
+    assert 0 < need < (1 << 20)
+    with emu_lib.scratch_budget(need):
+        cut = run(inputs, cap=len(one.dst))
+        batches = emu_lib.last_batches()
+    assert batches >= 3, batches
+    assert cut.rc == 0 and np.array_equal(cut.dst, one.dst) and np.array_equal(cut.out_off, one.out_off)
+    assert np.array_equal(cut.status, one.status) and np.array_equal(cut.bound, one.bound)
+    assert (one.status == 0).sum() >= len(items) and (one.status != 0).sum() >= len(bad)

@@ -73,6 +73,27 @@ def test_one_batch_of_everything(G):
     assert all(classes.get(c, 0) >= 10 for c in (R.OK, R.EOF, R.UNEXPECTED_EOF)), classes
 
 
+def test_budget_cuts_change_nothing(G):
+    """The batch of everything as one device batch and again under the least scratch budget the largest request fits alone (its
+    chunk records and clip slots plus the 1/8 allowance, as the sequence reports it): at least three batches; the same bytes,
+    layout, `got` and statuses.  One byte less changes nothing either: the device form of the ranged reads never refuses a request
+    for size — the one that does not fit runs as a batch of its own (only the host-buffer form has a ceiling, a quarter of the
+    budget for a request's slice and range)."""
+    streams, indexes, requests, want = R.everything(G)
+    one = run(streams, indexes, requests)
+    assert one.rc == 0 and emu_lib.last_batches() == 1
+    need = emu_lib.last_max_need()
+    assert 0 < need < (1 << 20)
+    for budget in (need, need - 1):
+        with emu_lib.scratch_budget(budget):
+            cut = run(streams, indexes, requests)
+            batches = emu_lib.last_batches()
+        assert batches >= 3, (budget, batches)
+        assert cut.rc == 0 and np.array_equal(cut.dst, one.dst) and np.array_equal(cut.out_off, one.out_off)
+        assert np.array_equal(cut.got, one.got) and np.array_equal(cut.status, one.status)
+    R.check(one, requests, want)
+
+
 def test_corrupt_input_under_a_dense_index(G):
     """480 single-bit mutations, seed 0x52D0002, of the seven small streams read through their dense indexes (s2_range_cases.corrupt_cases);
     the judge is the reference's sequential Reader over the stream's identifier + mutated[first covered header : cut].  The reference

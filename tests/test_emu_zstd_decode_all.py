@@ -6,6 +6,8 @@ import zipfile
 
 import pytest
 
+import emu_lib
+import zstd_frame_cases as zc
 from zstd_frame_cases import emu_decode_all as decode_all
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -73,3 +75,31 @@ def test_bad_frames_are_refused(G):
     outs, status = decode_all([z for _, z in bad], 1 << 16)
     assert all(int(s) != 0 for s in status), [NAMES[int(s)] for s in status]
     assert outs == [b""] * 44
+
+
+def test_budget_cuts_change_nothing_and_refuse_what_cannot_fit(G):
+    """The hand-built frames (tests/zstd_frame_cases.py) as one device batch, then under the least scratch budget that refuses no input
+    — the largest input's staging and per-frame scratch plus the 1/8 allowance, as the sequence reports it: at least three batches,
+    the same bytes, layout and statuses.  One byte less: exactly that input is KC_ZD_SIZE_EXCEEDED with an empty range, every other
+    input as before."""
+    cs = [c for c in zc.cases() if not c.big]
+    inputs = [c.data for c in cs]
+    dicts = [zc.raw_dict_blob(i, d) for i, d in zc.DICTS.items()]
+    refs = [zc.reference(G, c) for c in cs]
+    cap = sum(len(r) for r, _ in refs if r is not None)
+    outs, status = decode_all(inputs, cap, dicts=dicts)
+    assert emu_lib.last_batches() == 1 and not zc.judge(cs, refs, outs, status)
+    need = emu_lib.last_max_need()
+    k = max(range(len(cs)), key=lambda i: len(outs[i]))  # the input that needs it: the one with the most decoded bytes
+    decode_all([inputs[k]], cap, dicts=dicts)
+    assert emu_lib.last_max_need() == need and 0 < need < (16 << 20) and int(status[k]) == 0
+    with emu_lib.scratch_budget(need):
+        outs2, status2 = decode_all(inputs, cap, dicts=dicts)
+        assert emu_lib.last_batches() >= 3, emu_lib.last_batches()
+    assert outs2 == outs and list(status2) == list(status)
+    with emu_lib.scratch_budget(need - 1):
+        outs3, status3 = decode_all(inputs, cap, dicts=dicts)
+        assert emu_lib.last_batches() >= 3
+    assert NAMES[int(status3[k])] == "SIZE_EXCEEDED" and outs3[k] == b""
+    assert [o for i, o in enumerate(outs3) if i != k] == [o for i, o in enumerate(outs) if i != k]
+    assert [int(s) for i, s in enumerate(status3) if i != k] == [int(s) for i, s in enumerate(status) if i != k]

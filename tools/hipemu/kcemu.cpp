@@ -18,7 +18,6 @@
 #include "../../compress_amd/csrc/kc_zstd_plan.hip"
 #include "../../compress_amd/csrc/kc_zstd_decode_all.hip"
 #include "../../compress_amd/csrc/kc_dict.cpp"       // (host code: the dictionary loader the decoder options use)
-#include "../../compress_amd/csrc/kc_zdec_host.h"
 #include "../../compress_amd/csrc/kc_zstd_dstream.hip"
 #include "../../compress_amd/csrc/kc_zdstream_host.h"
 #include "../../compress_amd/csrc/kc_s2_plan.hip"
@@ -29,94 +28,19 @@
 #include "../../compress_amd/csrc/kc_s2rstream_host.h"
 #include "../../compress_amd/csrc/kc_flate_inflate.hip"
 
-// s2.Reader / s2.Decode over n inputs on the emulator: the plan kernel (both passes), the decode kernel with its CRC, the verdict per
-// input (first failing chunk in stream order, else the plan's error) and the zero-fill of the failed ranges — kc_s2_dec_api.cpp's
-// sequence as one batch in plain memory.  Returns 0, -2 when dst_cap is too small (nothing written).
-static int kcemu_s2_decode(const KcS2PlanParams& P0, int ignore_crc, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* bound, uint32_t* status) {
-    KcS2PlanParams P = P0;
-    const uint32_t n = P.n;
-    std::vector<uint32_t> nc(n + 1, 0), st(n + 1, 0), chunk0(n + 1, 0);
-    std::vector<uint64_t> bd(n + 1, 0);
-    P.n_chunks = nc.data(); P.bound = bd.data(); P.status = st.data();
-    kc_launch_s2_plan(P, nullptr);
-    uint32_t total = 0;
-    out_off[0] = 0;
-    for (uint32_t i = 0; i < n; i++) { chunk0[i] = total; total += nc[i]; out_off[i + 1] = out_off[i] + bd[i]; bound[i] = bd[i]; }
-    if (out_off[n] > dst_cap) return -2;
-    std::vector<KcS2Chunk> ch(total + 1);
-    std::vector<uint32_t> cs(total + 1, 0xA7A7A7A7u);
-    if (total) {
-        P.chunk0 = chunk0.data(); P.out0 = out_off; P.chunks = ch.data();
-        kc_launch_s2_plan(P, nullptr);
-        KcS2DecodeAllParams D;
-        memset(&D, 0, sizeof(D));
-        D.src = P.src; D.chunks = ch.data(); D.n_chunks = total; D.dst = dst; D.ignore_crc = ignore_crc; D.status = cs.data();
-        kc_launch_s2_decode_all(D, nullptr);
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        uint32_t v = 0;
-        for (uint32_t k = 0; k < nc[i] && !v; k++) v = cs[chunk0[i] + k];
-        if (!v) v = st[i];
-        status[i] = v;
-        if (v && bd[i]) memset(dst + out_off[i], 0, (size_t)bd[i]);
-    }
-    return 0;
-}
+#include "../../compress_amd/csrc/kc_s2dec_host.h"
+#include "../../compress_amd/csrc/kc_s2ranges_host.h"
+#include "../../compress_amd/csrc/kc_flate_host.h"
 
-// flate.NewReader / gzip.NewReader over n inputs on the emulator: the sizing pass, the exclusive scan of its sizes, the write pass with
-// its CRC-32 and zero-fill — kc_flate_api.cpp's sequence as one batch in plain memory.  Returns 0, -2 when dst_cap is too small
-// (nothing written).
-static int kcemu_flate(KcFlateParams P, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* bound, uint32_t* status, uint64_t* consumed) {
-    const uint32_t n = P.n;
-    std::vector<uint64_t> size(n + 1, 0), used(n + 1, 0);
-    std::vector<uint32_t> st(n + 1, 0xA7A7A7A7u), mem(n + 1, 0), wst(n + 1, 0xA7A7A7A7u);
-    P.size = size.data(); P.status = st.data(); P.consumed = used.data(); P.members = mem.data();
-    kc_launch_flate_size(P, nullptr);
-    out_off[0] = 0;
-    for (uint32_t i = 0; i < n; i++) { out_off[i + 1] = out_off[i] + size[i]; bound[i] = size[i]; status[i] = st[i]; if (consumed) consumed[i] = used[i]; }
-    if (!dst) return 0;  // the bound alone
-    if (out_off[n] > dst_cap) return -2;
-    P.out0 = out_off; P.dst = dst; P.wstatus = wst.data();
-    kc_launch_flate_write(P, nullptr);
-    for (uint32_t i = 0; i < n; i++)
-        if (mem[i]) { status[i] = wst[i]; if (wst[i] && consumed) consumed[i] = 0; }
-    return 0;
-}
-
-// The stream reader's device over plain memory: every buffer exactly as large as asked for (a write outside it is one outside a heap
-// block), copies are memcpy, the kernels run on the emulator.
-struct KcemuZsDevice : KcZsDevice {
-    void* buf[B_N] = {nullptr};
-    size_t cap[B_N] = {0};
+// The decoders' device (kc_decdev_host.h) over plain memory: every buffer a heap block of exactly the size asked for (a write outside
+// it is one outside a heap block), filled with 0xA7 when it is made; copies are memcpy; the kernels run on the emulator.
+static uint64_t g_budget = 0;   // kcemu_set_scratch_budget: what the batch decoders may ask for (0: anything)
+static KcDecTimes g_last;       // what the last batch decoder's sequence reported
+struct KcemuDevice : KcDecDevice {
+    std::vector<void*> buf;
+    std::vector<size_t> cap;
     int reserve(int which, size_t bytes, void** p) override {
-        if (cap[which] < bytes) {
-            free(buf[which]);
-            buf[which] = malloc(bytes);
-            cap[which] = bytes;
-            memset(buf[which], 0xA7, bytes);
-        }
-        *p = buf[which];
-        return buf[which] ? 0 : -6;
-    }
-    int h2d(void* d, const void* h, size_t n) override { if (n) memcpy(d, h, n); return 0; }
-    int d2h(void* h, const void* d, size_t n) override { if (n) memcpy(h, d, n); return 0; }
-    int d2d(void* d, const void* s, size_t n) override { if (n) memcpy(d, s, n); return 0; }
-    void entropy(const KcZsEntropyParams& P) override { kc_launch_zstd_dstream_entropy(P, nullptr); }
-    void execute(const KcZsExecParams& P) override { kc_launch_zstd_dstream_execute(P, nullptr); }
-    void hash(const KcZsHashParams& P) override { kc_launch_xxh64_stream(P, nullptr); }
-    int sync() override { return 0; }
-    ~KcemuZsDevice() override { for (void* b : buf) free(b); }
-};
-struct KcemuZsStream {
-    KcemuZsDevice dev;
-    KcZsStream s;
-};
-
-// The S2 stream reader's device over plain memory, in the same way.
-struct KcemuS2rDevice : KcS2rDevice {
-    void* buf[B_N] = {nullptr};
-    size_t cap[B_N] = {0};
-    int reserve(int which, size_t bytes, void** p) override {
+        if ((size_t)which >= buf.size()) { buf.resize(which + 1, nullptr); cap.resize(which + 1, 0); }
         if (cap[which] < bytes || !buf[which]) {
             free(buf[which]);
             buf[which] = malloc(bytes ? bytes : 1);
@@ -128,95 +52,85 @@ struct KcemuS2rDevice : KcS2rDevice {
     }
     int h2d(void* d, const void* h, size_t n) override { if (n) memcpy(d, h, n); return 0; }
     int d2h(void* h, const void* d, size_t n) override { if (n) memcpy(h, d, n); return 0; }
-    void launch(const KcS2RstreamParams& P) override { kc_launch_s2_rstream(P, nullptr); }
+    int d2d(void* d, const void* s, size_t n) override { if (n) memcpy(d, s, n); return 0; }
+    int zero(void* d, size_t n) override { if (n) memset(d, 0, n); return 0; }
     int sync() override { return 0; }
-    ~KcemuS2rDevice() override { for (void* b : buf) free(b); }
+    uint64_t budget() override { return g_budget ? g_budget : UINT64_MAX; }
+    void lane_group(int lanes) override { hipemu::set_group(lanes); }
+    ~KcemuDevice() override { for (void* b : buf) free(b); }
+};
+struct KcemuZsStream {
+    KcemuDevice dev;
+    KcZsStream s;
 };
 struct KcemuS2rStream {
-    KcemuS2rDevice dev;
+    KcemuDevice dev;
     KcS2rStream s;
 };
 
+// n_dicts dictionaries back to back (dict_off: n_dicts + 1 offsets) into the decoder's options: full-format ones, or raw ones
+// (WithDecoderDictRaw) as "KCRD", id, content.  False on a dictionary the loader refuses.
+static bool kcemu_load_dicts(KcZdOpts& o, const uint8_t* dict_blobs, const uint64_t* dict_off, uint32_t n_dicts) {
+    for (uint32_t k = 0; k < n_dicts; k++) {
+        const uint8_t* blob = dict_blobs + dict_off[k];
+        const uint64_t blen = dict_off[k + 1] - dict_off[k];
+        if (blen >= 8 && memcmp(blob, "KCRD", 4) == 0) {
+            uint32_t id;
+            memcpy(&id, blob + 4, 4);
+            if (kc_zd_add_dict_raw(o, id, blob + 8, blen - 8) != 0) return false;
+            continue;
+        }
+        KcZdDict D;
+        const uint8_t* content = nullptr;
+        uint64_t clen = 0;
+        if (kc_dict_load_decoder(blob, blen, &D, &content, &clen) != 0 || kc_zd_add_dict(o, D, content, clen) != 0) return false;
+    }
+    return true;
+}
+
+// s2.Reader / s2.Decode over n inputs: kc_s2dec_host.h's sequence over plain memory.  bound: the planned layout's sizes.
+static int kcemu_s2_decode(const KcS2dMode& m, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off,
+                           uint64_t* bound, uint32_t* status) {
+    KcemuDevice dev;
+    g_last = KcDecTimes();
+    const int rc = kc_s2d_decode(&dev, m, src, in_off, n, dst, dst_cap, out_off, status, g_last);
+    if (rc == 0 || rc == KC_ERR_DST_TOO_SMALL)
+        for (uint32_t i = 0; i < n; i++) bound[i] = out_off[i + 1] - out_off[i];
+    return rc;
+}
+
+// flate.NewReader / gzip.NewReader over n inputs: kc_flate_host.h's sequence over plain memory.  dst null: the sizing pass alone.
+static int kcemu_flate(const KcFlOpts& o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off,
+                       uint64_t* bound, uint32_t* status, uint64_t* consumed) {
+    KcemuDevice dev;
+    g_last = KcDecTimes();
+    if (!dst) return kc_fl_inflate(&dev, o, src, in_off, n, nullptr, 0, nullptr, status, consumed, bound, g_last);
+    const int rc = kc_fl_inflate(&dev, o, src, in_off, n, dst, dst_cap, out_off, status, consumed, nullptr, g_last);
+    if (rc == 0 || rc == KC_ERR_DST_TOO_SMALL)
+        for (uint32_t i = 0; i < n; i++) bound[i] = out_off[i + 1] - out_off[i];
+    return rc;
+}
+
 extern "C" {
 
-// zstd.Decoder.DecodeAll over n inputs on the emulator: the plan kernel (both passes), the decode kernel, XXH64 of the decoded frames,
-// the host's verdict per input (kc_zdec_host.h) and the compaction into dst — kc_zstd_dec_api.cpp's sequence as one batch in plain
-// memory.  dict_blobs: n_dicts full-format dictionaries back to back (dict_off: n_dicts + 1 offsets), all registered at once.
-// Returns 0, -2 when dst_cap is too small, -1 on a dictionary the loader refuses.
+// The scratch budget of the batch decoders' sequences in bytes (KC_OPT_MAX_SCRATCH_MIB's part on the device); 0: unlimited.
+void kcemu_set_scratch_budget(uint64_t bytes) { g_budget = bytes; }
+// What the last batch decoder call reported: the device batches it was cut into, and the largest single input's scratch with its
+// 1/8 allowance (the least budget under which no input is refused for size).
+int kcemu_last_batches() { return g_last.batches; }
+uint64_t kcemu_last_max_need() { return g_last.max_need; }
+
+// zstd.Decoder.DecodeAll over n inputs: kc_zdec_host.h's sequence over plain memory.  dict_blobs: as kcemu_load_dicts takes them, all
+// registered at once.  Returns 0, -2 when dst_cap is too small, -1 on a dictionary the loader refuses.
 int kcemu_zstd_decode_all(const uint8_t* src, const uint64_t* in_off, uint32_t n, uint64_t max_memory, uint64_t max_window, int ignore_checksum,
                           const uint8_t* dict_blobs, const uint64_t* dict_off, uint32_t n_dicts, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off,
                           uint32_t* status) {
-    std::vector<KcZdDict> dicts(n_dicts);
-    std::vector<uint8_t> arena(16);
-    for (uint32_t k = 0; k < n_dicts; k++) {
-        const uint8_t* content = nullptr;
-        uint64_t clen = 0;
-        const uint8_t* blob = dict_blobs + dict_off[k];
-        const uint64_t blen = dict_off[k + 1] - dict_off[k];
-        if (blen >= 8 && memcmp(blob, "KCRD", 4) == 0) {  // a raw dictionary (WithDecoderDictRaw): "KCRD", id, content
-            memset(&dicts[k], 0, sizeof(dicts[k]));
-            memcpy(&dicts[k].id, blob + 4, 4);
-            dicts[k].rep[0] = 1; dicts[k].rep[1] = 4; dicts[k].rep[2] = 8;
-            dicts[k].content_len = (uint32_t)(blen - 8);
-            content = blob + 8;
-            clen = blen - 8;
-        } else if (kc_dict_load_decoder(blob, blen, &dicts[k], &content, &clen) != 0) return -1;
-        dicts[k].content_off = arena.size();
-        arena.insert(arena.end(), content, content + clen);
-        arena.resize((arena.size() + 15) & ~(size_t)15);
-    }
-    std::vector<uint32_t> nf(n + 1, 0), exact(n + 1, 0), st(n + 1, 0), frame0(n + 1, 0);
-    std::vector<uint64_t> bound(n + 1, 0), slotb(n + 1, 0), slot0(n + 1, 0);
-    KcZdPlanParams P;
-    memset(&P, 0, sizeof(P));
-    P.src = src; P.in_off = in_off; P.n = n; P.max_memory = max_memory; P.max_window = max_window;
-    P.dicts = n_dicts ? dicts.data() : nullptr; P.n_dicts = n_dicts;
-    P.n_frames = nf.data(); P.bound = bound.data(); P.slot_bytes = slotb.data(); P.exact = exact.data(); P.status = st.data();
-    kc_launch_zstd_plan(P, nullptr);
-    uint32_t nfr = 0;
-    uint64_t slots = 0;
-    for (uint32_t i = 0; i < n; i++) { frame0[i] = nfr; slot0[i] = slots; nfr += nf[i]; slots += slotb[i]; }
-    std::vector<KcZdFrame> fr(nfr + 1);
-    std::vector<uint8_t> stage(slots + 64, 0xA7), lits((size_t)(nfr + 1) * KC_ZD_LIT_STRIDE, 0xA7);
-    std::vector<uint32_t> fsize(nfr + 1, 0), fstatus(nfr + 1, 0), fcrc(nfr + 1, 0), csize(nfr + 1, 0);
-    std::vector<uint64_t> hoff(2 * (size_t)nfr + 2, 0), hash(2 * (size_t)nfr + 2, 0), soff(nfr + 1, 0), ooff(nfr + 1, 0);
-    if (nfr) {
-        P.frame0 = frame0.data(); P.slot0 = slot0.data(); P.frames = fr.data();
-        kc_launch_zstd_plan(P, nullptr);
-        KcZdDecodeParams D;
-        memset(&D, 0, sizeof(D));
-        D.src = src; D.frames = fr.data(); D.n_frames = nfr; D.stage = stage.data(); D.lits = lits.data(); D.dicts = dicts.data();
-        D.dict_arena = arena.data(); D.max_memory = max_memory; D.out_size = fsize.data(); D.status = fstatus.data(); D.crc_stored = fcrc.data();
-        D.hash_off = hoff.data();
-        kc_launch_zstd_decode_all(D, nullptr);
-        if (!ignore_checksum) {
-            hipemu::set_group(4);
-            kc_launch_xxh64(stage.data(), hoff.data(), 2 * nfr - 1, hash.data(), nullptr);
-            hipemu::set_group(64);
-        }
-    }
-    uint64_t pos = 0;
-    out_off[0] = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        uint64_t total = 0;
-        if (st[i] == 0 && nf[i]) {
-            const uint32_t f0 = frame0[i];
-            st[i] = kc_zd_settle_input(fr.data() + f0, fstatus.data() + f0, fsize.data() + f0, fcrc.data() + f0, hash.data() + 2 * (size_t)f0, nf[i],
-                                       max_memory, ignore_checksum != 0, &total);
-            if (st[i]) total = 0;
-        }
-        if (pos + total > dst_cap) return -2;
-        for (uint32_t f = frame0[i]; f < frame0[i] + nf[i]; f++) {
-            soff[f] = fr[f].slot_off;
-            ooff[f] = pos;
-            csize[f] = st[i] ? 0u : fsize[f];
-            pos += csize[f];
-        }
-        status[i] = st[i];
-        out_off[i + 1] = pos;
-    }
-    kc_launch_compact(stage.data(), soff.data(), csize.data(), ooff.data(), dst, nfr, nullptr);
-    return 0;
+    KcZdOpts o;
+    o.max_memory = max_memory; o.max_window = max_window; o.ignore_checksum = ignore_checksum;
+    if (!kcemu_load_dicts(o, dict_blobs, dict_off, n_dicts)) return -1;
+    KcemuDevice dev;
+    g_last = KcDecTimes();
+    return kc_zd_decode_all(&dev, o, src, in_off, n, dst, dst_cap, out_off, status, g_last);
 }
 
 // The verifier over n units on the emulator, one frame each and every frame's decoded length given (dst_off): the decode kernel, XXH64 of
@@ -243,33 +157,14 @@ int kcemu_zstd_decode_units(const uint8_t* enc, const uint64_t* enc_off, uint32_
 }
 
 // zstd.NewReader(r) on the emulator: kc_zstd_dstream_new / _feed / _free of include/kcgpu.h without the context — the state machine of
-// kc_zdstream_host.h over KcemuZsDevice.  blocks: blocks per launch (KC_OPT_DSTREAM_BLOCKS); the dictionaries as kcemu_zstd_decode_all
+// kc_zdstream_host.h over KcemuDevice.  blocks: blocks per launch (KC_OPT_DSTREAM_BLOCKS); the dictionaries as kcemu_zstd_decode_all
 // takes them.  Returns null on a dictionary the loader refuses.
 void* kcemu_zstd_dstream_new(uint64_t max_memory, uint64_t max_window, int ignore_checksum, uint32_t blocks, const uint8_t* dict_blobs,
                              const uint64_t* dict_off, uint32_t n_dicts) {
     KcemuZsStream* z = new KcemuZsStream();
     z->s.dev = &z->dev;
     z->s.o.max_memory = max_memory; z->s.o.max_window = max_window; z->s.o.ignore_checksum = ignore_checksum; z->s.o.blocks = blocks;
-    z->s.o.dicts.resize(n_dicts);
-    z->s.o.arena.assign(16, 0);
-    for (uint32_t k = 0; k < n_dicts; k++) {
-        KcZdDict& D = z->s.o.dicts[k];
-        const uint8_t* content = nullptr;
-        uint64_t clen = 0;
-        const uint8_t* blob = dict_blobs + dict_off[k];
-        const uint64_t blen = dict_off[k + 1] - dict_off[k];
-        if (blen >= 8 && memcmp(blob, "KCRD", 4) == 0) {  // a raw dictionary (WithDecoderDictRaw): "KCRD", id, content
-            memset(&D, 0, sizeof(D));
-            memcpy(&D.id, blob + 4, 4);
-            D.rep[0] = 1; D.rep[1] = 4; D.rep[2] = 8;
-            D.content_len = (uint32_t)(blen - 8);
-            content = blob + 8;
-            clen = blen - 8;
-        } else if (kc_dict_load_decoder(blob, blen, &D, &content, &clen) != 0) { delete z; return nullptr; }
-        D.content_off = z->s.o.arena.size();
-        z->s.o.arena.insert(z->s.o.arena.end(), content, content + clen);
-        z->s.o.arena.resize((z->s.o.arena.size() + 15) & ~(size_t)15);
-    }
+    if (!kcemu_load_dicts(z->s.o, dict_blobs, dict_off, n_dicts)) { delete z; return nullptr; }
     return z;
 }
 int kcemu_zstd_dstream_feed(void* h, const uint8_t* src, uint64_t n, int eof, uint8_t* dst, uint64_t dst_cap, uint64_t* consumed, uint64_t* produced,
@@ -280,7 +175,7 @@ int kcemu_zstd_dstream_reset(void* h) { ((KcemuZsStream*)h)->s.reset(); return 0
 void kcemu_zstd_dstream_free(void* h) { delete (KcemuZsStream*)h; }
 
 // s2.NewReader(r).Read / Skip on the emulator: kc_s2_rstream_new / _feed / _skip / _skip_left / _on_skippable / _reset / _free of
-// include/kcgpu.h without the context — the state machine of kc_s2rstream_host.h over KcemuS2rDevice.  chunks: data chunks per launch
+// include/kcgpu.h without the context — the state machine of kc_s2rstream_host.h over KcemuDevice.  chunks: data chunks per launch
 // (KC_OPT_S2_RSTREAM_CHUNKS); max_buf: MaxEncodedLen(max_block) + 4.
 void* kcemu_s2_rstream_new(uint32_t max_block, uint32_t max_buf, int ignore_crc, int ignore_id, uint32_t chunks) {
     if (chunks < 1 || chunks > 4096) return nullptr;
@@ -302,105 +197,49 @@ void kcemu_s2_rstream_free(void* h) { delete (KcemuS2rStream*)h; }
 
 int kcemu_s2_decode_streams(const uint8_t* src, const uint64_t* in_off, uint32_t n, uint32_t max_block, uint32_t max_buf, int ignore_crc, int ignore_id,
                             uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* bound, uint32_t* status) {
-    KcS2PlanParams P;
-    memset(&P, 0, sizeof(P));
-    P.src = src; P.in_off = in_off; P.n = n; P.max_block = max_block; P.max_buf = max_buf; P.ignore_id = ignore_id;
-    return kcemu_s2_decode(P, ignore_crc, dst, dst_cap, out_off, bound, status);
+    KcS2dMode m;
+    m.max_block = max_block; m.max_buf = max_buf; m.ignore_crc = ignore_crc; m.ignore_id = ignore_id;
+    return kcemu_s2_decode(m, src, in_off, n, dst, dst_cap, out_off, bound, status);
 }
 
 // N x io.ReadAll(flate.NewReaderDict(input, dict)); dst null: the sizing pass alone
 int kcemu_flate_inflate(const uint8_t* src, const uint64_t* in_off, uint32_t n, const uint8_t* dict, uint32_t dict_len, uint8_t* dst, uint64_t dst_cap,
                         uint64_t* out_off, uint64_t* bound, uint32_t* status, uint64_t* consumed) {
-    KcFlateParams P;
-    memset(&P, 0, sizeof(P));
+    KcFlOpts o;
     if (dict_len > 32768) { dict += dict_len - 32768; dict_len = 32768; }
-    P.src = src; P.in_off = in_off; P.n = n; P.dict = dict; P.dict_len = dict_len;
-    return kcemu_flate(P, dst, dst_cap, out_off, bound, status, consumed);
+    o.dict = dict; o.dict_len = dict_len;
+    return kcemu_flate(o, src, in_off, n, dst, dst_cap, out_off, bound, status, consumed);
 }
 // N x io.ReadAll(gzip.NewReader(input)) under Multistream(multistream)
 int kcemu_gzip_inflate(const uint8_t* src, const uint64_t* in_off, uint32_t n, int multistream, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off,
                        uint64_t* bound, uint32_t* status, uint64_t* consumed) {
-    KcFlateParams P;
-    memset(&P, 0, sizeof(P));
-    P.src = src; P.in_off = in_off; P.n = n; P.gzip = 1; P.multistream = multistream != 0;
-    return kcemu_flate(P, dst, dst_cap, out_off, bound, status, consumed);
+    KcFlOpts o;
+    o.gzip = true; o.multistream = multistream;
+    return kcemu_flate(o, src, in_off, n, dst, dst_cap, out_off, bound, status, consumed);
 }
 
-// s2.ReadSeeker.ReadAt over m requests on the emulator: Index.Find per request, the ranged plan (both passes), the clipped decode,
-// the verdict per request and the zero-fills — kc_s2_ranges_api.cpp's sequence as one batch in plain memory.  Returns 0, -2 when
+// s2.ReadSeeker.ReadAt over m requests: kc_s2ranges_host.h's layout, Index.Find and sequence over plain memory.  Returns 0, -2 when
 // dst_cap is too small (nothing written), -1 for a request that names no input or wraps.
 int kcemu_s2_read_ranges(const uint8_t* src, const uint64_t* in_off, uint32_t n_streams, const kc_s2_index* const* index, const uint32_t* req_stream,
                          const uint64_t* req_off, const uint64_t* req_len, uint32_t m, uint32_t max_block, uint32_t max_buf, int ignore_crc, int ignore_id,
                          uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* got, uint32_t* status) {
-    out_off[0] = 0;
-    for (uint32_t j = 0; j < m; j++) {
-        if (req_stream[j] >= n_streams || req_off[j] + req_len[j] < req_off[j]) return -1;
-        out_off[j + 1] = out_off[j] + req_len[j];
-    }
-    if (out_off[m] > dst_cap) return -2;
-    std::vector<KcS2Req> Q;
-    std::vector<uint32_t> live;
-    for (uint32_t j = 0; j < m; j++) {
-        const uint32_t s = req_stream[j];
-        KcS2Req q;
-        memset(&q, 0, sizeof(q));
-        q.front = in_off[s]; q.end = in_off[s + 1]; q.pos = q.front; q.off = req_off[j]; q.len = req_len[j]; q.out0 = out_off[j];
-        if (index && index[s]) {
-            int64_t cc = 0, uu = 0;
-            const int rc = q.off > (uint64_t)INT64_MAX ? (int)KC_S2I_UNEXPECTED_EOF : kc_s2_index_find(index[s], (int64_t)q.off, &cc, &uu);
-            if (rc) {
-                status[j] = (uint32_t)rc; got[j] = 0;
-                if (q.len) memset(dst + out_off[j], 0, (size_t)q.len);
-                continue;
-            }
-            if (cc > 0) { q.pos = (uint64_t)cc > q.end - q.front ? q.end : q.front + (uint64_t)cc; q.flags = KC_S2R_MID; }
-            q.u = (uint64_t)uu;
-        }
-        live.push_back(j);
-        Q.push_back(q);
-    }
-    const uint32_t n = (uint32_t)Q.size();
-    if (n == 0) return 0;
-    std::vector<KcS2ReqPlan> H(n);
-    KcS2RangePlanParams P;
-    memset(&P, 0, sizeof(P));
-    P.src = src; P.reqs = Q.data(); P.m = n; P.max_block = max_block; P.max_buf = max_buf; P.ignore_id = ignore_id; P.plan = H.data();
-    kc_launch_s2_range_plan(P, nullptr);
-    uint32_t nc = 0;
-    uint64_t slots = 0;
-    for (uint32_t i = 0; i < n; i++) { Q[i].chunk0 = nc; Q[i].slot0 = slots; nc += H[i].n_chunks; slots += H[i].slot_bytes; }
-    std::vector<KcS2RChunk> ch(nc + 1);
-    std::vector<uint32_t> cs(nc + 1, 0xA7A7A7A7u);
-    uint8_t* slot = (uint8_t*)malloc(slots ? slots : 1);  // exactly the slots: a write outside them is one outside a heap block
-    if (nc) {
-        P.plan = nullptr; P.chunks = ch.data();
-        kc_launch_s2_range_plan(P, nullptr);
-        KcS2RangeDecodeParams D;
-        memset(&D, 0, sizeof(D));
-        D.src = src; D.chunks = ch.data(); D.n_chunks = nc; D.dst = dst; D.slots = slot; D.ignore_crc = ignore_crc; D.status = cs.data();
-        kc_launch_s2_range_decode(D, nullptr);
-    }
-    free(slot);
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t j = live[i];
-        uint32_t v = 0;
-        for (uint32_t k = 0; k < H[i].n_chunks && !v; k++) v = cs[Q[i].chunk0 + k];
-        if (!v) v = H[i].status;
-        status[j] = v;
-        uint64_t g = (v == KCS2D_OK || v == KCS2D_EOF) ? H[i].got : 0;
-        if (g > Q[i].len) g = Q[i].len;
-        got[j] = g;
-        if (g < Q[i].len) memset(dst + out_off[j] + g, 0, (size_t)(Q[i].len - g));
-    }
-    return 0;
+    std::vector<KcS2Req> R;
+    std::vector<uint32_t> pre;
+    const char* why = "";
+    const int rc = kc_s2r_resolve(in_off, n_streams, index, req_stream, req_off, req_len, m, dst_cap, out_off, R, pre, &why);
+    g_last = KcDecTimes();
+    if (rc != 0 || m == 0) return rc;
+    KcS2dMode o;
+    o.max_block = max_block; o.max_buf = max_buf; o.ignore_crc = ignore_crc; o.ignore_id = ignore_id;
+    KcemuDevice dev;
+    return kc_s2r_read(&dev, o, src, R, pre, dst, out_off, got, status, g_last);
 }
 
 int kcemu_s2_decode_blocks_all(const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint64_t* bound,
                                uint32_t* status) {
-    KcS2PlanParams P;
-    memset(&P, 0, sizeof(P));
-    P.src = src; P.in_off = in_off; P.n = n; P.blocks = 1;
-    return kcemu_s2_decode(P, 1, dst, dst_cap, out_off, bound, status);
+    KcS2dMode m;
+    m.blocks = 1;
+    return kcemu_s2_decode(m, src, in_off, n, dst, dst_cap, out_off, bound, status);
 }
 
 // kc_zstd_prime_kernel: n table slots (zeroed by the caller) primed from the first unit_hist[u] bytes of their units; reverse = the

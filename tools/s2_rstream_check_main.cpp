@@ -34,9 +34,9 @@ struct Rng {
     uint32_t below(uint32_t n) { return n ? next() % n : 0; }
 };
 
-struct HeapDevice : KcS2rDevice {
-    void* buf[B_N] = {nullptr};
-    size_t cap[B_N] = {0};
+struct HeapDevice : KcDecDevice {
+    void* buf[RS_N] = {nullptr};
+    size_t cap[RS_N] = {0};
     int reserve(int which, size_t bytes, void** p) override {  // exactly what is asked for, every time
         free(buf[which]);
         buf[which] = malloc(bytes ? bytes : 1);
@@ -46,7 +46,8 @@ struct HeapDevice : KcS2rDevice {
     }
     int h2d(void* d, const void* h, size_t n) override { if (n) memcpy(d, h, n); return 0; }
     int d2h(void* h, const void* d, size_t n) override { if (n) memcpy(h, d, n); return 0; }
-    void launch(const KcS2RstreamParams& P) override { kc_launch_s2_rstream(P, nullptr); }
+    int d2d(void* d, const void* s, size_t n) override { if (n) memcpy(d, s, n); return 0; }
+    int zero(void* d, size_t n) override { if (n) memset(d, 0, n); return 0; }
     int sync() override { return 0; }
     ~HeapDevice() override { for (void* b : buf) free(b); }
 };

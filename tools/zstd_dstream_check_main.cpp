@@ -30,9 +30,9 @@ struct Rng {
     uint32_t below(uint32_t n) { return n ? next() % n : 0; }
 };
 
-struct HeapDevice : KcZsDevice {
-    void* buf[B_N] = {nullptr};
-    size_t cap[B_N] = {0};
+struct HeapDevice : KcDecDevice {
+    void* buf[ZS_N] = {nullptr};
+    size_t cap[ZS_N] = {0};
     int reserve(int which, size_t bytes, void** p) override {
         if (cap[which] < bytes || !buf[which]) {
             free(buf[which]);
@@ -45,9 +45,7 @@ struct HeapDevice : KcZsDevice {
     int h2d(void* d, const void* h, size_t n) override { if (n) memcpy(d, h, n); return 0; }
     int d2h(void* h, const void* d, size_t n) override { if (n) memcpy(h, d, n); return 0; }
     int d2d(void* d, const void* s, size_t n) override { if (n) memcpy(d, s, n); return 0; }
-    void entropy(const KcZsEntropyParams& P) override { kc_launch_zstd_dstream_entropy(P, nullptr); }
-    void execute(const KcZsExecParams& P) override { kc_launch_zstd_dstream_execute(P, nullptr); }
-    void hash(const KcZsHashParams& P) override { kc_launch_xxh64_stream(P, nullptr); }
+    int zero(void* d, size_t n) override { if (n) memset(d, 0, n); return 0; }
     int sync() override { return 0; }
     ~HeapDevice() override { for (void* b : buf) free(b); }
 };

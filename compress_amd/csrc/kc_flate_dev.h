@@ -471,7 +471,7 @@ __device__ __forceinline__ uint32_t fl_input(const KcFlateParams& P, const uint6
             }
         }
         if (ended) {
-            if (done) break;
+            if (done) { *used = end - begin; break; }  // the file ends there, and the reader has read all of it looking for the string's end
             return KCFL_EOF;
         }
         if (flg & 2u) {

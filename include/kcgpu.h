@@ -642,6 +642,12 @@ enum {
  * The reference's own quirk is kept: an input that ends inside the extra bits of a length or distance, or inside a fixed block's
  * five distance bits, ends with the raw io.EOF (inflate_gen.go:114-122, 142-151, 210-219), so ReadAll returns what was decoded
  * WITHOUT an error: KC_FL_OK.  (gzip then misses its trailer: KC_FL_EOF.)
+ * One divergence from the reference, observed against its own code (profiles/flate_reference_parity.md): a symbol read through an
+ * EMPTY Huffman table — a match in a dynamic block without a distance code, a block without a literal/length code, a header without
+ * a code-length code — is KC_FL_CORRUPT, as in RFC 1951 and zlib.  The reference's huffmanDecoder.init returns on an empty code before
+ * it clears the table (inflate.go:154-156), so it decodes such a symbol through what that decoder held last — the previous dynamic
+ * block's distance code, the same block's code-length code, the previous literal/length code — and accepts some of these inputs,
+ * answers others with io.ErrUnexpectedEOF or a flate.InternalError.  No encoder writes such a block.
  * kc_flate_inflate_bound[_dev]: the sizing pass alone — bound[i] = the exact decoded size of every input that stands, status[i] its
  * verdict, consumed[i] as above.
  * The host-buffer forms stage the inputs in groups cut between inputs: a group's input bytes (first sweep, the sizes) and its input
@@ -658,7 +664,9 @@ kc_status kc_flate_inflate_bound(kc_ctx* ctx, const kc_flate_ropts* o, const uin
                                  uint64_t* bound, uint32_t* status, uint64_t* consumed);
 /* kc_gzip_inflate[_dev] == io.ReadAll(gzip.NewReader(bytes.NewReader(input))) for every input, under Multistream (gzip/gunzip.go:94-124
  * NewReader / Reset, :183-253 readHeader, :255-295 Read: the trailer, the next member).  Arguments and output as above.
- * consumed[i] runs through the last trailer read; with Multistream off, what lies behind it is the next member's header.
+ * consumed[i] runs through the last trailer read; with Multistream off, what lies behind it is the next member's header.  One input
+ * is read further and still stands: behind a complete member, a next header whose name or comment runs into the input's end is the
+ * reference's raw io.EOF (gunzip.go:157-160) — the file ends there, and consumed[i] is the whole input, which the reader has read.
  * The sizing pass walks headers, streams, trailers and the ISIZE compare, member after member; the write pass computes the CRC-32 of
  * every member's bytes and compares it with the trailer (KC_FL_CHECKSUM: the planned range is zero-filled).  An input that fails
  * behind complete members keeps their range, zero-filled.  kc_gzip_inflate_bound[_dev]: the sizing pass alone — the first error short

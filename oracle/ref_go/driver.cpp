@@ -361,6 +361,59 @@ void* dec_thread(void* a) {
 }
 }  // namespace
 
+#ifndef GOREF_AMD64  // (inflate and gunzip: in the portable flavour only)
+namespace {
+// io.ReadAll(flate.NewReaderDict(r, dict)) and gzip.NewReader(r) / Multistream(ms) / io.ReadAll: the reference's inflate and gunzip as
+// the judge of tests/flate_model.py.  r is this reader over a []byte: Read and ReadByte (a flate.Reader, so that neither package wraps
+// it in a bufio.Reader) that counts what it hands out — `consumed`, the number of input bytes the reference has read when it stops.
+struct ByteSource {
+    go::Slice<go::byte> buf;
+    long long pos = 0;
+    std::tuple<go::Int, go::error> Read(go::Slice<go::byte> p) {  // bytes.Reader.Read
+        if (pos >= buf.n) return std::tuple<go::Int, go::error>(go::Int(go::K(0LL)), io::EOF_);
+        const long long k = p.n < buf.n - pos ? p.n : buf.n - pos;
+        if (k > 0) memcpy((void*)p.p, (const void*)(buf.p + pos), (size_t)k);
+        pos += k;
+        return std::tuple<go::Int, go::error>(go::Int::raw(k), go::error());
+    }
+    std::tuple<go::byte, go::error> ReadByte() {  // bytes.Reader.ReadByte
+        if (pos >= buf.n) return std::tuple<go::byte, go::error>(go::byte::raw(0), io::EOF_);
+        return std::tuple<go::byte, go::error>(buf.p[pos++], go::error());
+    }
+};
+// the classes of tests/flate_model.py; INTERNAL (flate.InternalError, a panic) is one no test expects
+enum { FL_OK = 0, FL_CORRUPT = 1, FL_EOF = 2, FL_HEADER = 3, FL_CHECKSUM = 4, FL_INTERNAL = 99 };
+int flate_class(const go::error& e) {
+    if (e == go::nil || e == io::EOF_) return FL_OK;  // ReadAll: io.EOF is the end, not an error
+    if (e == flate::errCorrupt) return FL_CORRUPT;
+    if (e == io::ErrUnexpectedEOF) return FL_EOF;
+    if (e == gzip::ErrHeader) return FL_HEADER;
+    if (e == gzip::ErrChecksum) return FL_CHECKSUM;
+    return FL_INTERNAL;
+}
+void flate_init() {
+    go::rt::Permanent perm;  // the fixed Huffman decoder (a sync.Once) and the package variables outlive the call
+    flate::go_init(); gzip::go_init();
+    flate::fixedHuffmanDecoderInit();
+}
+// io.ReadAll: Read until an error; what was read in front of it is returned with it
+template <class R> long long read_all(R* r, uint8_t* out, long long cap, go::error* err) {
+    go::Slice<go::byte> chunk = go::make_slice<go::byte>(512);
+    long long total = 0;
+    for (;;) {
+        auto t = r->Read(chunk);
+        const long long k = std::get<0>(t).v;
+        if (k > 0) {
+            if (total + k > cap) return -2;
+            memcpy(out + total, chunk.p, (size_t)k);
+            total += k;
+        }
+        if (std::get<1>(t) != go::nil) { *err = std::get<1>(t); return total; }
+    }
+}
+}  // namespace
+#endif
+
 #ifdef GOREF_AMD64
 // The assembly addresses the fields of these structures by the offsets Go's compiler gives them.  The translation keeps Go's field
 // order and types (gort.h: I<T> is T, Slice is base / len / cap, Array is the elements), so the C++ compiler lays them out the same
@@ -567,4 +620,76 @@ long long goref_zstd_encode_stream(const uint8_t* src, long long n, uint8_t* dst
 }
 // the NEXT goref_zstd_encode_stream call feeds its input from this offset on through Encoder.ReadFrom (one-shot; -1: Write only)
 void goref_zstd_next_stream_readfrom(long long at) { g_readfrom_at = at; }
+#ifndef GOREF_AMD64
+// io.ReadAll(flate.NewReaderDict(bytes, dict)): returns the decoded length — on an error too, the bytes in front of it, as ReadAll returns
+// them — the class (0 OK, 1 CORRUPT, 2 EOF, 99 internal) in *err and the input bytes read in *consumed; -2: out is too small
+long long goref_flate_inflate(const uint8_t* src, long long n, const uint8_t* dict, long long dict_len, uint8_t* out, long long cap, long long* consumed, int* err) {
+    using namespace go;
+    rt::Scope scope;
+    ByteSource source;
+    *err = FL_INTERNAL;
+    *consumed = 0;
+    try {
+        flate_init();
+        source.buf = make_slice<byte>(n);
+        if (n) memcpy((void*)source.buf.p, src, (size_t)n);
+        Slice<byte> d;  // (nil without a dictionary, like NewReader)
+        if (dict != nullptr && dict_len > 0) { d = make_slice<byte>(dict_len); memcpy((void*)d.p, dict, (size_t)dict_len); }
+        flate::decompressor* f = flate::NewReaderDict(flate::Reader(&source), d);
+        error e;
+        const long long total = read_all(f, out, cap, &e);
+        *consumed = source.pos;
+        if (total >= 0) *err = flate_class(e);
+        return total;
+    } catch (const go::Panic&) {
+        *consumed = source.pos;
+        return -1;
+    }
+}
+// z, err := gzip.NewReader(bytes); z.Multistream(ms); io.ReadAll(z): like goref_flate_inflate, with the classes 3 HEADER and 4 CHECKSUM
+// (io.EOF out of NewReader: 2 EOF).  hdr receives the first member's header where NewReader succeeded: ModTime (4 bytes, little-endian
+// seconds), OS, 1 if Extra is not nil, then Extra, Name, Comment, each behind its 2-byte length; *hdr_len its size, 0 without a header
+long long goref_gunzip(const uint8_t* src, long long n, int multistream, uint8_t* out, long long cap, long long* consumed, int* err,
+                       uint8_t* hdr, long long hdr_cap, long long* hdr_len) {
+    using namespace go;
+    rt::Scope scope;
+    ByteSource source;
+    *err = FL_INTERNAL;
+    *consumed = 0;
+    *hdr_len = 0;
+    try {
+        flate_init();
+        source.buf = make_slice<byte>(n);
+        if (n) memcpy((void*)source.buf.p, src, (size_t)n);
+        auto r = gzip::NewReader(flate::Reader(&source));
+        gzip::Reader* z = std::get<0>(r);
+        if (std::get<1>(r) != nil) {
+            *consumed = source.pos;
+            *err = std::get<1>(r) == io::EOF_ ? FL_EOF : flate_class(std::get<1>(r));
+            return 0;
+        }
+        {
+            std::string h;
+            const uint32_t mt = (uint32_t)z->Hdr.ModTime.v;
+            h.append((const char*)&mt, 4);
+            h += (char)z->Hdr.OS.v;
+            h += (char)(z->Hdr.Extra != nil ? 1 : 0);
+            auto put = [&](const char* p, size_t k) { const uint16_t l = (uint16_t)k; h.append((const char*)&l, 2); h.append(p, k); };
+            put((const char*)z->Hdr.Extra.p, (size_t)z->Hdr.Extra.n);
+            put(z->Hdr.Name.s.data(), z->Hdr.Name.s.size());
+            put(z->Hdr.Comment.s.data(), z->Hdr.Comment.s.size());
+            if ((long long)h.size() <= hdr_cap) { memcpy(hdr, h.data(), h.size()); *hdr_len = (long long)h.size(); }
+        }
+        z->Multistream(multistream != 0);
+        error e;
+        const long long total = read_all(z, out, cap, &e);
+        *consumed = source.pos;
+        if (total >= 0) *err = flate_class(e);
+        return total;
+    } catch (const go::Panic&) {
+        *consumed = source.pos;
+        return -1;
+    }
+}
+#endif
 }

@@ -256,8 +256,8 @@ class Emitter:
                 return "K(%dLL)" % self.iota
             if n in BUILTIN_TYPES and n not in self.pkg.types:
                 return BUILTIN_TYPES[n]
-            if n in getattr(self, "recv_methods", ()) and n in self.pkg.funcs:
-                return "%s::%s" % (mangle(self.pkg.name), mangle(n))
+            if n in getattr(self, "recv_methods", ()) and (n in self.pkg.funcs or any(n in d[1] for _, d in self.pkg.consts)):
+                return "%s::%s" % (mangle(self.pkg.name), mangle(n))  # a package function or constant named like a method of the receiver
         return mangle(n)
 
     def ex_paren(self, e):
@@ -784,7 +784,8 @@ class Emitter:
             temps = []
             for r in rhs:
                 t = self.newtmp()
-                self.w("auto %s = go::def(%s);" % (t, self.ex(r)))
+                # (a, b = 0, 0: an untyped constant takes the type of what it is assigned to, not int)
+                self.w(("auto %s = %s;" if r[0] in ("int", "rune") else "auto %s = go::def(%s);") % (t, self.ex(r)))
                 temps.append(t)
             for l, t in zip(lhs, temps):
                 if l != ("ident", "_"):
@@ -1576,12 +1577,12 @@ class Emitter:
         self.w("};")
         self.w("template <class T_> struct Impl_ : Base_ {")
         self.ind += 1
-        self.w("T_* p;")
-        self.w("explicit Impl_(T_* q) : p(q) {}")
-        self.w("void* obj_() override { return (void*)p; }")
+        self.w("T_* p_;")  # (not `p`: a method's parameter may have that name)
+        self.w("explicit Impl_(T_* q) : p_(q) {}")
+        self.w("void* obj_() override { return (void*)p_; }")
         self.w("const void* tid_() override { return go::type_tag<T_>(); }")
         for mn, rt, ps, an in sigs:
-            self.w("%s %s(%s) override { return p->%s(%s); }" % (rt, mn, ps, mn, an))
+            self.w("%s %s(%s) override { return p_->%s(%s); }" % (rt, mn, ps, mn, an))
         self.ind -= 1
         self.w("};")
         self.w("Base_* b_ = nullptr;")

@@ -338,6 +338,17 @@ inline Slice<byte> to_bytes(const String& s) { Slice<byte> r = make_slice<byte>(
 inline Slice<byte> to_bytes(const Slice<byte>& s) { return s; }
 inline String to_string(const Slice<byte>& b) { return String(std::string((const char*)b.p, (size_t)b.n)); }
 inline String to_string(const String& s) { return s; }
+inline String to_string(const Slice<I<int32_t>>& r) {  // string([]rune): UTF-8 (gzip's Latin-1 names: code points below 0x100)
+    std::string o;
+    for (long long i = 0; i < r.n; i++) {
+        const uint32_t c = (uint32_t)r.p[i].v;
+        if (c < 0x80) o += (char)c;
+        else if (c < 0x800) { o += (char)(0xC0 | (c >> 6)); o += (char)(0x80 | (c & 0x3F)); }
+        else if (c < 0x10000) { o += (char)(0xE0 | (c >> 12)); o += (char)(0x80 | ((c >> 6) & 0x3F)); o += (char)(0x80 | (c & 0x3F)); }
+        else { o += (char)(0xF0 | (c >> 18)); o += (char)(0x80 | ((c >> 12) & 0x3F)); o += (char)(0x80 | ((c >> 6) & 0x3F)); o += (char)(0x80 | (c & 0x3F)); }
+    }
+    return String(o);
+}
 template <class T> T* new_() { return new (rt::tag) T(); }
 template <class T, long long N> Array<T, N>& ix(Array<T, N>* p) { return *p; }
 template <class C> C&& ix(C&& c) { return std::forward<C>(c); }
@@ -431,6 +442,8 @@ inline Int OnesCount64(uint64 x) { return Int::raw(__builtin_popcountll(x.v)); }
 constexpr go::K UintSize(64);
 template <class S> uint32 RotateLeft32(uint32 x, S k) { const int s = (int)(go::idx(k) & 31); return uint32::raw((x.v << s) | (x.v >> ((32 - s) & 31))); }
 template <class S> uint64 RotateLeft64(uint64 x, S k) { const int s = (int)(go::idx(k) & 63); return uint64::raw((x.v << s) | (x.v >> ((64 - s) & 63))); }
+inline uint8 Reverse8(uint8 x) { uint8_t r = 0; for (int i = 0; i < 8; i++) r = (uint8_t)(r | (((x.v >> i) & 1u) << (7 - i))); return uint8::raw(r); }
+inline uint16 Reverse16(uint16 x) { uint16_t r = 0; for (int i = 0; i < 16; i++) r = (uint16_t)(r | (((x.v >> i) & 1u) << (15 - i))); return uint16::raw(r); }
 inline uint32 ReverseBytes32(uint32 x) { return uint32::raw(__builtin_bswap32(x.v)); }
 inline uint64 ReverseBytes64(uint64 x) { return uint64::raw(__builtin_bswap64(x.v)); }
 }  // namespace bits
@@ -575,7 +588,8 @@ static const go::error EOF_ = go::error(new go::ErrorObj{"EOF"});
 static const go::error ErrShortBuffer = go::error(new go::ErrorObj{"short buffer"});
 static const go::error ErrShortWrite = go::error(new go::ErrorObj{"short write"});
 // io.ReadFull (io.ReadAtLeast with min = len(buf)): EOF only if no byte was read, ErrUnexpectedEOF after a partial read
-inline std::tuple<go::Int, go::error> ReadFull(const Reader& r, const go::Slice<go::byte>& b) {
+// (any reader with Read: io.Reader, or a translated interface that has the method, like flate.Reader)
+template <class R> inline std::tuple<go::Int, go::error> ReadFull(R r, const go::Slice<go::byte>& b) {
     long long n = 0;
     go::error err;
     while (n < b.n && err == go::nil) {
@@ -588,7 +602,7 @@ inline std::tuple<go::Int, go::error> ReadFull(const Reader& r, const go::Slice<
     return {go::Int::raw(n), err};
 }
 }  // namespace io
-namespace crc32 {  // hash/crc32 of the Go standard library: table-driven, reflected (s2 uses the Castagnoli polynomial)
+namespace crc32 {  // hash/crc32 of the Go standard library: table-driven, reflected (s2 uses the Castagnoli polynomial, gzip IEEE)
 struct Table { uint32_t t[256]; };
 static constexpr go::K Castagnoli = go::K(0x82f63b78LL);
 inline Table* MakeTable(go::K poly) {
@@ -605,6 +619,8 @@ inline go::uint32 Update(go::uint32 crc, Table* tab, const go::Slice<go::byte>& 
     for (long long i = 0; i < p.n; i++) c = tab->t[(c ^ p.p[i].v) & 0xFF] ^ (c >> 8);
     return go::uint32::raw(~c);
 }
+static Table* const IEEETable = MakeTable(go::K(0xedb88320LL));
+inline go::uint32 ChecksumIEEE(const go::Slice<go::byte>& p) { return Update(go::uint32::raw(0), IEEETable, p); }
 }  // namespace crc32
 namespace rdebug {
 inline void PrintStack() {}

@@ -1,5 +1,6 @@
 """What go2cpp.py translates: the reference's Go files of the zstd encode path, per package in dependency order; declarations
-left out (decoder halves, goroutine variants, String() methods of debug output) and the few source patches, each with its reason."""
+left out (decoder halves, goroutine variants, String() methods of debug output) and the few source patches, each with its reason.
+Also the inflate side of flate and gzip's reader (portable flavour only): what io.ReadAll over flate.NewReaderDict / gzip.NewReader runs."""
 
 CFG = {
     "packages": [
@@ -13,6 +14,9 @@ CFG = {
                   "zstd/enc_better.go", "zstd/enc_best.go", "zstd/seqdec.go", "zstd/seqdec_generic.go", "zstd/dict.go", "zstd/bitreader.go", "zstd/bytebuf.go", "zstd/history.go",
                   "zstd/blockdec.go", "zstd/framedec.go", "zstd/fse_decoder.go",
                   "zstd/fse_decoder_generic.go", "zstd/encoder_options.go", "zstd/enc_jobs.go", "zstd/encoder.go", "zstd/decoder_options.go", "zstd/decoder.go"]),
+        # the inflate side of flate and gzip's reader: the judge of tests/flate_model.py (regmask_other.go: the shift masks of a non-amd64 build, all ones)
+        ("flate", ["flate/regmask_other.go", "flate/dict_decoder.go", "flate/inflate.go", "flate/inflate_gen.go"]),
+        ("gzip", ["gzip/gunzip.go"]),
     ],
     # path -> names of top-level declarations (or Type.method) that are not translated
     "skip": {
@@ -28,6 +32,12 @@ CFG = {
         "zstd/zstd.go": {"_", "byter"},                                   # an interface assertion on bytes.Buffer (decoder input)
         "zstd/encoder_options.go": {"EncoderLevelFromString", "EncoderLevel.String"},  # strings package
         "zstd/enc_jobs.go": {"Encoder.jobWorker", "Encoder.jobFlusher"},              # the worker and flusher goroutines (see the patches)
+        # aliases of compress/flate's error types (error VALUES here: see the patches); the Resetter interface (gzip calls Reset on the
+        # concrete type); the checkpoint / resume plumbing and WriteTo, which io.ReadAll never reaches
+        "flate/inflate.go": {"CorruptInputError", "InternalError", "ReadError", "WriteError", "Resetter", "InflateCheckpoint", "WithEobCallback",
+                             "WithResumeFrom", "decompressor.ResetCP", "decompressor.applyCP", "decompressor.WriteTo"},
+        "flate/dict_decoder.go": {"dictDecoder.appendWindow"},                        # only the checkpoint callback reads the window
+        "gzip/gunzip.go": {"crcer", "crcUpdater", "Reader.WriteTo", "Reader.Close", "le"},   # WriteTo and its digest plumbing; ReadAll goes through Read
     },
     # path -> the ONLY declarations taken from that file (the rest of it is the decoder / the streaming writer)
     "only": {
@@ -52,6 +62,8 @@ CFG = {
         "zstd/encoder.go": {"Encoder", "encoder", "encoderState", "Encoder.encodeAll", "Encoder.MaxEncodedSize", "Encoder.Reset", "Encoder.Write",
                             "Encoder.writeBlocks", "Encoder.writeJobs", "Encoder.nextBlock", "Encoder.Flush", "Encoder.flushJobs", "Encoder.Close",
                             "Encoder.closeJobs", "Encoder.ReadFrom", "Encoder.readFromJobs"},
+        # of the five copies of the block body, generated per concrete reader type, the generic one (the driver's reader is a flate.Reader)
+        "flate/inflate_gen.go": {"decompressor.huffmanGenericReader", "decompressor.huffmanBlockDecoder"},
         # constants and the block / literals type enumerations the encoder shares with the decoder
         # initPredefined builds the predefined DECODER tables first and copies their normalised counts into the encoders
     },
@@ -62,6 +74,8 @@ CFG = {
         "zstd.Encoder": {"encoders", "init"},              # the pool of encoders EncodeAll draws from (the driver hands it one)
         "zstd.encJob": {"done"},                           # job mode's worker plumbing: see the patches of zstd/enc_jobs.go
         "zstd.jobState": {"jobCh", "resultCh", "cond", "workerWg", "flusherWg", "inputPool", "outputPool", "overlapPool"},
+        "flate.decompressor": {"cb", "cp", "hasCP", "uncOffset", "cpBuf"},   # the checkpoint callback and resume state
+        "gzip.Reader": {"br"},                                              # the bufio.Reader of a source without ReadByte
 },
     # path -> [(regular expression, replacement, why)]: source patches applied before parsing
     "patches": {
@@ -138,6 +152,56 @@ CFG = {
             (r"// Index represents an S2/Snappy index\.\n", "type indexInfo struct {\n\tcompressedOffset   int64\n\tuncompressedOffset int64\n}\n\n// Index represents an S2/Snappy index.\n",
              "... declared here"),
         ],
+        # flate.NewReaderDict / gzip.NewReader over a flate.Reader (Read + ReadByte: the driver's byte-counting source).  Errors: the
+        # reference's CorruptInputError and InternalError are named types that carry an offset / a text; the translation has error
+        # VALUES, so each becomes one value (the class is all the driver reports).
+        "flate/inflate.go": [
+            (r'\t"bufio"\n\t"compress/flate"\n', '\t"errors"\n', "no bufio branch; compress/flate only lent its error types"),
+            (r"type CorruptInputError = flate\.CorruptInputError\n", 'var errCorrupt = errors.New("flate: corrupt input")\nvar errInternal = errors.New("flate: internal error")\n',
+             "the two error classes as values"),
+            (r"\tdebugDecode = false\n", "\tdebugDecode = false\n\n\tmaxMatchOffset = 1 << 15\n\tendBlockMarker = 256\n",
+             "two constants the decoder shares with the encoder, whose files (fast_encoder.go:44, huffman_bit_writer.go:20) are not translated"),
+            (r"type ReadError = flate\.ReadError\n", "", "deprecated alias, never returned"),
+            (r"type WriteError = flate\.WriteError\n", "", "likewise"),
+            (r"CorruptInputError\(f\.roffset\)", "errCorrupt", "a CorruptInputError at any offset is the class CORRUPT"),
+            (r'InternalError\("unexpected length code"\)', "errInternal", "the class `internal`"),
+            (r"type Reader interface \{\n\tio\.Reader\n\tio\.ByteReader\n\}", "type Reader interface {\n\tRead(p []byte) (int, error)\n\tReadByte() (byte, error)\n}",
+             "the two embedded interfaces spelt out (the translation writes one adapter per interface, by its methods)"),
+            (r"\tif f\.cb != nil \{.*?\n\t\}\n\n(\tf\.step = nextBlock\n)", r"\1", "finishBlock: no checkpoint callback"),
+            (r"\tcase huffmanBytesBuffer:.*?(\tcase huffmanGenericReader:)", r"\1", "doStep: the generic block body only"),
+            (r"func makeReader\(r io\.Reader\) Reader \{.*?\n\}\n", "func makeReader(r Reader) Reader {\n\treturn r\n}\n", "the source is a flate.Reader: no bufio branch"),
+            (r"Reset\(r io\.Reader, dict \[\]byte\) error \{", "Reset(r Reader, dict []byte) error {", "likewise"),
+            (r"\tif f\.hasCP \{.*?\n\t\}\n\n(\treturn &f\n)", r"\1", "NewReaderOpts: no resume checkpoint"),
+            (r"func NewReaderOpts\(r io\.Reader, opts \.\.\.ReaderOpt\) io\.ReadCloser", "func NewReaderOpts(r Reader, opts ...ReaderOpt) *decompressor",
+             "the concrete type instead of io.ReadCloser (gzip calls Reset on it without the Resetter assertion)"),
+            (r"func NewReader\(r io\.Reader\) io\.ReadCloser", "func NewReader(r Reader) *decompressor", "likewise"),
+            (r"func NewReaderDict\(r io\.Reader, dict \[\]byte\) io\.ReadCloser", "func NewReaderDict(r Reader, dict []byte) *decompressor", "likewise"),
+        ],
+        "flate/inflate_gen.go": [
+            (r"\tfr := f\.r\.\(Reader\)\n", "\tfr := f.r\n", "f.r is a Reader already"),
+            (r"CorruptInputError\(f\.roffset\)", "errCorrupt", "see flate/inflate.go"),
+            (r"(func \(f \*decompressor\) huffmanBlockDecoder\(\) \{\n)\tswitch f\.r\.\(type\) \{.*?\n\t\}\n", r"\1\tf.huffmanGenericReader()\n",
+             "the type switch over concrete reader types: its Reader / default arm"),
+        ],
+        "gzip/gunzip.go": [
+            (r'\t"bufio"\n\t"compress/gzip"\n', '\t"errors"\n', "no bufio branch; compress/gzip only lent its two error values"),
+            (r'\t"time"\n', "", "Header.ModTime as the integer the header holds"),
+            (r"ErrChecksum = gzip\.ErrChecksum", 'ErrChecksum = errors.New("gzip: invalid checksum")', "compress/gzip's value"),
+            (r"ErrHeader = gzip\.ErrHeader", 'ErrHeader = errors.New("gzip: invalid header")', "compress/gzip's value"),
+            (r"var le = binary\.LittleEndian\n", "", "spelt out at its uses (next patch)"),
+            (r"\ble\.Uint", "binary.LittleEndian.Uint", "encoding/binary's little-endian loads"),
+            (r"ModTime time\.Time", "ModTime int64    ", "seconds since the epoch, as stored"),
+            (r"time\.Unix\((int64\(binary\.LittleEndian\.Uint32\(z\.buf\[4:8\]\)\)), 0\)", r"\1", "likewise"),
+            (r"decompressor io\.ReadCloser", "decompressor *flate.decompressor", "the concrete type (see flate/inflate.go)"),
+            (r"\tHeader       // valid after", "\tHdr Header   // valid after", "the embedded Header as a named field: Reset assigns it as a whole (an embedded struct is a base class here)"),
+            (r"z\.Header, z\.err = z\.readHeader\(\)", "z.Hdr, z.err = z.readHeader()", "likewise"),
+            (r"\t\tbr:           z\.br,\n", "", "no bufio.Reader"),
+            (r"\tif rr, ok := r\.\(flate\.Reader\); ok \{\n\t\tz\.r = rr\n\t\} else \{.*?\n\t\}\n(\tz\.Hdr, z\.err = z\.readHeader\(\))", r"\tz.r = r\n\1",
+             "Reset: the source is a flate.Reader"),
+            (r"func NewReader\(r io\.Reader\)", "func NewReader(r flate.Reader)", "likewise"),
+            (r"func \(z \*Reader\) Reset\(r io\.Reader\)", "func (z *Reader) Reset(r flate.Reader)", "likewise"),
+            (r"z\.decompressor\.\(flate\.Resetter\)\.Reset", "z.decompressor.Reset", "the concrete type has the method"),
+        ],
         "s2/hashtable_pool.go": [
             (r"= sync\.Pool\{New: func\(\) any \{ return &\w+\{\} \}\}", " sync.Pool",
              "sync.Pool is an allocation cache: its New hook is not needed when Get is replaced by a fresh table (next patch)"),
@@ -163,6 +227,8 @@ def flavour(name):
             "zstd/matchlen_generic.go": ["zstd/matchlen_amd64.go"]}
     pk = []
     for pname, files in cfg["packages"]:
+        if pname in ("flate", "gzip"):   # inflate has no assembly: the portable flavour alone holds it
+            continue
         out = []
         for f in files:
             out += swap.pop(f, [f])

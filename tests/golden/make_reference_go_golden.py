@@ -28,6 +28,18 @@ DICT_SEED = 0x5EED0005
 S2 = ["s2", "s2better", "s2snappy", "s2snappybetter", "s2best", "s2snappybest"]
 
 
+def flate_main():
+    """tests/golden/reference_go_flate_sha256.txt: one line `flate.<family> <sha256>` per case family of tests/flate_cases.py
+    (directed, mut, mutgz, generated, generated-gz), the hash over the records (name, class, consumed, len, sha256(bytes)) of the
+    REFERENCE's verdicts — io.ReadAll over flate.NewReaderDict / gzip.NewReader, translated (oracle_goref.flate_inflate / gunzip).
+    Run alone with:  python tests/golden/make_reference_go_golden.py flate      (half a minute)"""
+    import flate_cases as FC
+    with open(os.path.join(HERE, "reference_go_flate_sha256.txt"), "w") as f:
+        for name, cs in FC.families():
+            ref = lambda c: oracle_goref.gunzip(c.data, c.multistream) if c.fmt == "gzip" else oracle_goref.flate_inflate(c.data, c.dict)  # noqa: E731
+            f.write("flate.%s %s\n" % (name, FC.family_digest(cs, ref)))
+
+
 def main():
     lines = {}
     dct = _lib.corpus_fill("T", DICT_SEED, 0, 1, 64 << 10).tobytes()
@@ -72,4 +84,6 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] != ["flate"]:
+        main()
+    flate_main()

@@ -4,7 +4,9 @@ The library is the reference's Go source for the zstd encode path (encoder.go en
 enc_best, blockenc, fse_encoder, huff0, fse, xxhash) and for its portable-Go S2 block encoders (encode_all / encode_better /
 encode_best, encode_go), translated statement by statement into C++ at build time (oracle/ref_go/go2cpp.py; Go's integer,
 slice and array semantics in oracle/ref_go/gort.h) and compiled here (oracle/Makefile `ref`).  It is built where /root/reference
-exists (this container) and travels to the GPU box as a built file; nothing of the reference is stored in the repository."""
+exists (this container) and travels to the GPU box as a built file; nothing of the reference is stored in the repository.
+The portable flavour also holds the reference's inflate and gunzip (flate/inflate.go, inflate_gen.go, dict_decoder.go, gzip/gunzip.go):
+flate_inflate / gunzip below, the judge of tests/flate_model.py."""
 import ctypes as C
 import os
 import subprocess
@@ -89,6 +91,12 @@ def lib():
         L.goref_s2_read_stream.argtypes = [C.c_char_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_char_p, C.c_int]
         L.goref_s2_encode.restype = C.c_longlong
         L.goref_s2_encode.argtypes = [C.c_int, C.c_char_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_char_p, C.c_int]
+        if hasattr(L, "goref_flate_inflate"):
+            L.goref_flate_inflate.restype = C.c_longlong
+            L.goref_flate_inflate.argtypes = [C.c_char_p, C.c_longlong, C.c_char_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+        if hasattr(L, "goref_gunzip"):
+            L.goref_gunzip.restype = C.c_longlong
+            L.goref_gunzip.argtypes = [C.c_char_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
         _libs[key] = L
     if key == "amd64":
         L.goref_force_bmi(0 if _flavour == "amd64-nobmi" else -1)
@@ -297,3 +305,57 @@ def zstd_job_geometry(level=1, window_size=None):
 def calc_skippable_frame(written: int, want_multiple: int, s2=False) -> int:
     """calcSkippableFrame of the reference's zstd package (frameenc.go) or — s2=True — of its s2 package (writer.go); -1: it panicked."""
     return int(lib().goref_calc_skippable_frame(int(bool(s2)), int(written), int(want_multiple)))
+
+
+FL_INTERNAL = 99   # flate.InternalError or a panic: a class of its own that no test expects (the others are flate_model's numbers)
+
+
+def flate_available():
+    """The library is there and has the reference's inflate in it."""
+    return available() and hasattr(lib(), "goref_flate_inflate")
+
+
+def gunzip_available():
+    return available() and hasattr(lib(), "goref_gunzip")
+
+
+def flate_inflate(data: bytes, dict: bytes = b"", max_out: int = 1 << 20):
+    """io.ReadAll(flate.NewReaderDict(r, dict)) of the reference (flate/inflate.go, inflate_gen.go, dict_decoder.go, translated), r a
+    reader over `data` with Read and ReadByte that counts what it hands out -> (bytes, class, consumed): the bytes ReadAll returns (on
+    an error: what was decoded in front of it), flate_model's class number of the error (FL_INTERNAL: an InternalError or a panic) and
+    the number of input bytes the reference has read."""
+    data, dict = bytes(data), bytes(dict)
+    out = C.create_string_buffer(max_out)
+    consumed, err = C.c_longlong(0), C.c_int(0)
+    n = lib().goref_flate_inflate(data, len(data), dict or None, len(dict), out, max_out, C.byref(consumed), C.byref(err))
+    if n == -2:
+        raise ValueError("goref_flate_inflate: more than %d bytes" % max_out)
+    return (out.raw[:n] if n > 0 else b""), (FL_INTERNAL if n < 0 else err.value), consumed.value
+
+
+def gunzip(data: bytes, multistream=True, want_header=False, max_out: int = 1 << 20):
+    """z, err := gzip.NewReader(r); z.Multistream(multistream); io.ReadAll(z) of the reference (gzip/gunzip.go, translated) ->
+    (bytes, class, consumed) like flate_inflate; with want_header the first member's header fields as flate_model.gunzip gives them
+    (None where NewReader failed)."""
+    data = bytes(data)
+    out = C.create_string_buffer(max_out)
+    hdr = C.create_string_buffer(1 << 17)
+    consumed, err, hlen = C.c_longlong(0), C.c_int(0), C.c_longlong(0)
+    n = lib().goref_gunzip(data, len(data), int(bool(multistream)), out, max_out, C.byref(consumed), C.byref(err), hdr, 1 << 17, C.byref(hlen))
+    if n == -2:
+        raise ValueError("goref_gunzip: more than %d bytes" % max_out)
+    res = (out.raw[:n] if n > 0 else b""), (FL_INTERNAL if n < 0 else err.value), consumed.value
+    if not want_header:
+        return res
+    fields = None
+    if hlen.value:
+        h = hdr.raw[:hlen.value]
+        fields = {"ModTime": int.from_bytes(h[0:4], "little"), "OS": h[4]}
+        has_extra, at, parts = h[5], 6, []
+        for _ in range(3):
+            k = int.from_bytes(h[at:at + 2], "little")
+            parts.append(h[at + 2:at + 2 + k])
+            at += 2 + k
+        fields["Extra"] = parts[0] if has_extra else None
+        fields["Name"], fields["Comment"] = parts[1].decode("utf-8"), parts[2].decode("utf-8")
+    return res + (fields,)

@@ -1,7 +1,9 @@
 """flate / gzip inflate on the CPU wave emulator (tools/hipemu): the sizing pass, the scan and the write pass of
 compress_amd/csrc/kc_flate_inflate.hip as one batch in plain memory (kcemu_flate_inflate / kcemu_gzip_inflate), over every case of
-tests/flate_cases.py — the directed shapes, the 2 x 480 mutations, the large streams — judged by tests/flate_model.py: status,
-bytes, consumed and bound.  dst carries 0xA5 guards on both sides and stays untouched when the call fails."""
+tests/flate_cases.py — the directed shapes, the 2 x 480 mutations, the first 480 seeded structured streams raw and as gzip, the
+CRC-32 length sweep, the match-copy sweep, the large streams — judged by tests/flate_model.py with stale_tables=False (what the
+device implements; tests/test_ref_flate.py holds the model to the reference on the same cases): status, bytes, consumed and bound.
+dst carries 0xA5 guards on both sides and stays untouched when the call fails."""
 import ctypes as C
 
 import numpy as np
@@ -59,7 +61,7 @@ def run_batch(L, inputs, fmt, zdict, multistream):
 def judge(cases, results):
     bad = []
     for c, (got, st, used, bound, bst) in zip(cases, results):
-        want, cls, wused = FC.verdict(c)
+        want, cls, wused = FC.verdict(c, stale_tables=False)
         if cls == M.OK:
             ok = (got, st, used, bound, bst) == (want, M.OK, wused, len(want), M.OK)
         else:  # nothing decoded stays: an empty range, or a zero-filled one
@@ -100,10 +102,45 @@ def test_budget_changes_nothing(emu):
 
 
 @emu_lib._fanned(min_bytes=1)
-def _emu_many(items, fmt):
+def _emu_many(items, fmt, zdict=b"", multistream=True):
     """Independent inputs of one format in forked children, a share each (wall-clock time only)."""
     L = _declare(C.CDLL(emu_lib.build()))
-    return run_batch(L, [bytes(x) for x in items], fmt, b"", True)
+    return run_batch(L, [bytes(x) for x in items], fmt, zdict, multistream)
+
+
+def run_cases_fanned(cases):
+    FC.warm(cases)
+    for fmt, zdict, ms, cs in FC.batches(cases):
+        judge(cs, _emu_many([c.data for c in cs], fmt, zdict, ms))
+
+
+def test_generated_cases(emu):
+    """The first 480 seeded structured streams, raw and as gzip members: the share that holds 60 stale shapes per table (an empty
+    table behind a used one: CORRUPT here, whatever the reference reads through it) and the codes longer than the primary tables."""
+    fl, gz = FC.generated()[:480], FC.generated_gzip()[:480]
+    for tag in ("stale-dist", "stale-lit", "stale-clen"):
+        assert sum(1 for c in fl if tag in c.name) == 60
+    for tag in ("longL", "longD"):
+        assert sum(1 for c in fl if tag in c.name.split("/", 2)[2].split("+") and FC.verdict(c)[1] == M.OK) >= 30
+    run_cases_fanned(fl)
+    run_cases_fanned(gz)
+
+
+def test_crc32_length_sweep(emu):
+    cs = FC.crc_sweep()
+    assert len(cs) == 3 * len(FC.CRC_SWEEP_LENGTHS) + 3 * len(FC.CRC_SWEEP_TWINS)
+    run_cases_fanned(cs)
+    res = dict(zip((c.name for c in cs), _emu_many([c.data for c in cs], "gzip")))
+    for n in FC.CRC_SWEEP_TWINS:
+        for first in (1, 2, 3):
+            got, st = res["crc/len%d-first%d-bad-crc" % (n, first)][:2]
+            assert (got, st) == (bytes(first + n), M.CHECKSUM)
+
+
+def test_match_copy_sweep(emu):
+    cs = FC.copy_sweep()
+    assert len(cs) == 12 * 8 * 2 and all(FC.verdict(c)[1] == M.OK for c in cs)
+    run_cases_fanned(cs)
 
 
 def test_mutations(emu):

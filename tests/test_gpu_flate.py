@@ -1,7 +1,9 @@
 """flate / gzip inflate on the device (kc_flate_inflate*, kc_gzip_inflate*, compress_amd.flate / compress_amd.gzip): the cases of
 tests/flate_cases.py — the ones the CPU wave emulator runs (tests/test_emu_flate.py) — device-resident and through the host-buffer
-forms, batches of mixed good and bad inputs, the scratch ceiling, DST_TOO_SMALL and the reader objects.  tests/flate_model.py is the
-judge; its verdicts are computed once on the host (flate_cases.verdict)."""
+forms, batches of mixed good and bad inputs, the scratch ceiling, DST_TOO_SMALL and the reader objects; the 2 x 2000 seeded
+structured streams, the CRC-32 length sweep and the match-copy sweep.  tests/flate_model.py with stale_tables=False is the judge
+(what the device implements; tests/test_ref_flate.py holds the model to the reference's own code on the same cases); its verdicts
+are computed once on the host (flate_cases.verdict)."""
 import io
 
 import numpy as np
@@ -60,7 +62,7 @@ def run_device(inputs, fmt, zdict=b"", multistream=True, cap=None):
 def judge(cases, results):
     bad = []
     for c, (got, st, used, bound, bst) in zip(cases, results):
-        want, cls, wused = FC.verdict(c)
+        want, cls, wused = FC.verdict(c, stale_tables=False)
         if cls == M.OK:
             ok = (got, st, used, bound, bst) == (want, M.OK, wused, len(want), M.OK)
         else:  # nothing decoded stays: an empty range, or (gzip, behind complete members) a zero-filled one
@@ -166,7 +168,7 @@ def judge_host(cases, results):
     """The host forms hand out bytes or an error: status, bytes and consumed."""
     bad = []
     for c, (got, st, used, _, bst) in zip(cases, results):
-        want, cls, wused = FC.verdict(c)
+        want, cls, wused = FC.verdict(c, stale_tables=False)
         ok = (got, st, used) == ((want, 0, wused) if cls == M.OK else (b"", cls, 0)) and (bst == cls or cls == M.CHECKSUM)
         if not ok:
             bad.append((c.name, M.NAMES[cls], st, len(got), used))
@@ -198,6 +200,50 @@ def test_host_buffer_forms(kclib):
     assert outs[names.index("gzip/two-members")] == b"hello, " + b"world" * 100
     bound, status, used = gzip.GunzipBounds(src, off)
     assert int(bound[names.index("gzip/two-members")]) == 507 and int(used[names.index("gzip/two-members")]) == len(gzs[names.index("gzip/two-members")].data)
+
+
+def test_generated_cases_device(kclib):
+    """generated(seed, 2000) raw and as gzip members, one launch per batch (format, dictionary, Multistream), device-resident."""
+    for cases in (FC.generated(), FC.generated_gzip()):
+        assert len(cases) == 2000
+        for fmt, zdict, ms, cs in FC.batches(cases):
+            rc, res = run_device([c.data for c in cs], fmt, zdict, ms)
+            assert rc == 0
+            judge(cs, res)
+
+
+def test_generated_cases_host_forms(kclib):
+    for cases in (FC.generated(), FC.generated_gzip()):
+        for fmt, zdict, ms, cs in FC.batches(cases):
+            b = batch_of(fmt, zdict, ms)
+            try:
+                judge_host(cs, host_results(b, cs))
+            finally:
+                b.close()
+
+
+def test_crc32_length_sweep_device(kclib):
+    """The write pass's CRC-32 at the lengths where its split over the lanes changes (flate_cases.crc_sweep), the member's bytes at
+    every residue mod 4 in dst; a trailer CRC with one bit flipped is CHECKSUM and leaves the planned range zero-filled."""
+    cs = FC.crc_sweep()
+    rc, res = run_device([c.data for c in cs], "gzip")
+    assert rc == 0
+    judge(cs, res)
+    by_name = dict(zip((c.name for c in cs), res))
+    for n in FC.CRC_SWEEP_TWINS:
+        for first in (1, 2, 3):
+            got, st = by_name["crc/len%d-first%d-bad-crc" % (n, first)][:2]
+            assert (got, st) == (bytes(first + n), M.CHECKSUM)
+    assert {(len(FC.verdict(c)[0])) for c in cs if FC.verdict(c)[1] == M.OK} >= {1 + 65535, 3 + 512, 2 + 769}
+
+
+def test_match_copy_sweep_device(kclib):
+    cs = FC.copy_sweep()
+    assert all(FC.verdict(c)[1] == M.OK for c in cs)
+    for fmt, zdict, ms, b in FC.batches(cs):
+        rc, res = run_device([c.data for c in b], fmt, zdict, ms)
+        assert rc == 0
+        judge(b, res)
 
 
 def test_host_call_cut_into_groups(kclib):

@@ -74,17 +74,14 @@ kc_status check_supported(kc_ctx* c, const kc_zstd_opts* o) {
     // (the reference takes any dictionary below 2 GiB as history, zstd/dict.go:27, enc_base.go:160-198; here the dictionary is staged in
     // front of every unit of a batch, which the scratch budget accounts for — 64 MiB keeps positions inside the LDS kernel's field too)
     if (o->dict_len > ((uint64_t)64 << 20)) { c->err = "dictionary larger than 64 MiB not served by the device path"; return KC_ERR_UNSUPPORTED; }
-    if (o->block_size < 1024 || o->block_size > kMaxCompressedBlockSize || o->window_size < kMinWindowSize) { c->err = "bad block/window size"; return KC_ERR_BAD_ARG; }
+    if (o->block_size < 1024 || o->block_size > KC_ZSTD_MAX_BLOCK_SIZE || o->window_size < KC_ZSTD_MIN_WINDOW_SIZE) { c->err = "bad block/window size"; return KC_ERR_BAD_ARG; }
     return KC_OK;
 }
 
 
 // Match finders: sub-wave groups (8 lanes per unit), per-unit hash tables in an HBM arena that is zeroed (or primed from the
 // dictionary tables) before every launch.
-size_t match_table_bytes(int level) {
-    if (level == KC_SPEED_BEST) return 0;  // persistent slots (ensure_best_slots), not per unit
-    return level == KC_SPEED_BETTER ? kc_zbetter_table_bytes() : (level == KC_SPEED_DEFAULT ? kc_zdfast_table_bytes() : kc_zfast_table_bytes());
-}
+// (match_table_bytes: kc_host.h over kc_zenc_host.h — SpeedBestCompression has persistent slots, ensure_best_slots, not per-unit tables)
 
 // SpeedFastest: which kernel serves a launch of n_launch units.  The LDS-table kernel (one wave per unit, a few ms per unit
 // whatever the batch) wins while the units in flight cannot cover the HBM-table kernel's latency; the crossover is measured
@@ -258,7 +255,7 @@ void launch_match_kernel(kc_ctx* c, const KcMatchParams& mp, uint32_t slot0, uin
             ml.epoch = c->fast_epoch_now;
             ml.xseg_k = (int32_t)c->cfg.zfast_xseg_k;
             ml.empty_filter = c->cfg.zfast_filter != 0;
-            ml.tuned = c->cfg.zfast_variant < 0 ? (c->last_incompressible ? 1 : 0) : (int32_t)c->cfg.zfast_variant;
+            ml.tuned = zenc_tuned_form(c->cfg.zfast_variant, c->last_incompressible);
             kc_launch_zfast_match_grp(ml, (uint32_t*)((uint8_t*)c->tables.p + (size_t)slot0 * match_table_bytes(level)), n_launch, st);
         }
         return;
@@ -281,7 +278,7 @@ void launch_match_kernel(kc_ctx* c, const KcMatchParams& mp, uint32_t slot0, uin
         mf.epoch = c->fast_epoch_now;
         mf.xseg_k = (int32_t)c->cfg.zfast_xseg_k;
         mf.empty_filter = c->cfg.zfast_filter != 0;
-        mf.tuned = c->cfg.zfast_variant < 0 ? (c->last_incompressible ? 1 : 0) : (int32_t)c->cfg.zfast_variant;
+        mf.tuned = zenc_tuned_form(c->cfg.zfast_variant, c->last_incompressible);
         kc_launch_zfast_match_grp(mf, (uint32_t*)tab, n_launch, st);
     }
 }
@@ -296,377 +293,272 @@ kc_status launch_match(kc_ctx* c, const KcMatchParams& mp, const uint64_t* unit_
     return KC_OK;
 }
 
-// Blocks of one stream with Flush points (zstd/encoder.go): writeBlocks cuts a block every blockSize bytes after the last Flush
-// (:226-253); a Flush that finds nothing buffered does nothing (:552).  Close: a single block still buffered with no header
-// written yet is the EncodeAll frame (:272-288), otherwise the stream frame, with an empty last block when nothing is buffered
-// (:315-329).  Appends the block starts to *starts; *flags: bit 0 stream frame, bit 1 empty last block.  Returns the block count.
-uint32_t plan_stream_blocks(uint64_t bs, uint64_t len, const uint64_t* cuts, uint64_t n_cuts, std::vector<uint32_t>* starts, uint32_t* flags) {
-    uint64_t pos = 0, ci = 0, lastStart = 0;
-    uint32_t ub = 0;
-    while (pos < len) {
-        uint64_t e = pos + bs;
-        while (ci < n_cuts && cuts[ci] <= pos) ci++;
-        if (ci < n_cuts && cuts[ci] < e) e = cuts[ci];
-        if (e > len) e = len;
-        if (starts) starts->push_back((uint32_t)pos);
-        lastStart = pos;
-        pos = e;
-        ub++;
+// ---- batch_begin: the rules are kc_zenc_host.h's; each step below enqueues on the context's stream what its name says ----
+
+// every buffer whose size the plan alone decides
+static kc_status begin_reserve(kc_ctx* c, const kc_zstd_opts* o, const Plan& pl, const ChunkFeed* feed) {
+    const size_t n_units = pl.n_units, nb = pl.n_blocks;
+    const KcZencReserve r = zenc_reserve(o, pl);
+    kc_status s;
+    if ((s = ensure(c, c->unit_off, (n_units + 1) * 8)) || (s = ensure(c, c->unit_blk0, (n_units + 1) * 4)) ||
+        (s = ensure(c, c->stage_off, (n_units + 1) * 8)) || (s = ensure(c, c->out_off, (n_units + 1 + (feed ? feed->cut.size() : 0)) * 8)) ||
+        (s = ensure(c, c->seqs, r.seqs)) || (s = ensure(c, c->aux, r.aux)) || (s = ensure(c, c->lits, r.lits)) || (s = ensure(c, c->meta, r.meta)) ||
+        (s = ensure(c, c->stage, r.stage + 64)) || (s = ensure(c, c->out_size, n_units * 4)) ||
+        (s = ensure(c, c->xxh, n_units * 8)) || (s = ensure(c, c->redo, n_units * 4)) ||
+        (s = ensure(c, c->redo_blk, nb + 1)) || (s = ensure(c, c->pop_blk, nb + 1)) || (s = ensure(c, c->unit_list, n_units * 4)) ||
+        (s = ensure(c, c->predef, kc_fse_predef_bytes())) || (s = ensure(c, c->errflag, 64)))
+        return s;
+    return KC_OK;
+}
+
+// the predefined FSE tables once per context, the Flush points' block grid, and of the layout arrays what changed
+static kc_status begin_upload(kc_ctx* c, const Plan& pl, hipStream_t st) {
+    const size_t n_units = pl.n_units, nb = pl.n_blocks;
+    if (!c->predef_ready) {
+        kc_launch_fse_predef_init(c->predef.p, st);
+        c->predef_ready = true;
     }
-    const bool flushedAtEnd = n_cuts > 0 && cuts[n_cuts - 1] >= len;
-    const bool tailBuffered = ub > 0 && !flushedAtEnd && (len - lastStart) < bs;
-    const bool streamU = len > 0 && !(ub == 1 && tailBuffered);
-    *flags = (streamU ? 1u : 0u) | ((streamU && !tailBuffered) ? 2u : 0u);
-    return ub;
+    if (pl.irregular) {
+        kc_status s;
+        if ((s = ensure(c, c->blk_start, (nb + 1) * 4)) || (s = ensure(c, c->unit_flags, n_units * 4))) return s;
+        if (nb) HIPCHK(c, hipMemcpyAsync(c->blk_start.p, pl.blk_start.data(), nb * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(c->unit_flags.p, pl.unit_flags.data(), n_units * 4, hipMemcpyHostToDevice, st));
+    }
+    // the layout arrays: batches of equal-sized units repeat them exactly (every step of a fixed-size workload), and a copy from
+    // pageable memory stalls the host for tens of microseconds each — upload only what differs from what the device holds
+    struct Up { std::vector<uint8_t>& held; const void* host; size_t bytes; void* dev; const void*& held_dev; };
+    const Up ups[3] = {{c->up_unit_off, pl.rel_off.data(), (n_units + 1) * 8, c->unit_off.p, c->up_ptr[0]},
+                       {c->up_blk0, pl.blk0.data(), (n_units + 1) * 4, c->unit_blk0.p, c->up_ptr[1]},
+                       {c->up_stage_off, pl.stage_off.data(), (n_units + 1) * 8, c->stage_off.p, c->up_ptr[2]}};
+    for (const Up& u : ups) {
+        if (u.dev == u.held_dev && u.held.size() == u.bytes && memcmp(u.held.data(), u.host, u.bytes) == 0) continue;
+        HIPCHK(c, hipMemcpyAsync(u.dev, u.host, u.bytes, hipMemcpyHostToDevice, st));
+        u.held.assign((const uint8_t*)u.host, (const uint8_t*)u.host + u.bytes);
+        u.held_dev = u.dev;
+    }
+    // (the flag arrays of the batch are zeroed by one launch further down: kc_launch_clear)
+    return KC_OK;
+}
+
+// dictionary (raw content, WithEncoderDictRaw): the kernels read dict || unit per unit from the work buffer
+static kc_status begin_dictionary(kc_ctx* c, const kc_zstd_opts* o, const Plan& pl, const uint8_t* d_src, hipStream_t st, KcZencBufs& b) {
+    const uint32_t n_units = pl.n_units;
+    const int hist0 = pl.hist0, pos_bits = pl.pos_bits;
+    kc_status s;
+    std::vector<uint64_t> woff(n_units + 1);
+    for (uint32_t i = 0; i <= n_units; i++) woff[i] = pl.rel_off[i] + (uint64_t)i * (uint64_t)hist0;
+    if ((s = ensure(c, c->work, zenc_reserve(o, pl).work + 64)) || (s = ensure(c, c->work_off, (n_units + 1) * 8)) ||
+        (s = ensure(c, c->dictbuf, (size_t)hist0 + 64)) || (s = ensure(c, c->proto, kc_zbetter_table_bytes())))
+        return s;
+    HIPCHK(c, hipMemcpyAsync(c->work_off.p, woff.data(), (n_units + 1) * 8, hipMemcpyHostToDevice, st));
+    // The dictionary's content and its pristine tables (betterFastEncoderDict.Reset, enc_better.go:1114-1183, in the device entry
+    // format) are the same from batch to batch: rebuilt and uploaded only when the dictionary, the level, the position width or the
+    // stamp mode changed (round 6: the rolling host pipeline runs a batch per 256 MiB — 4 MiB of host table building, two uploads
+    // and a stream synchronisation per batch before).
+    const bool epochMode = better_epoch_mode(c, o->level, pos_bits, hist0);
+    uint64_t key = 0xcbf29ce484222325ULL;
+    for (int i = 0; i < hist0; i++) key = (key ^ o->dict[i]) * 0x100000001b3ULL;
+    key ^= ((uint64_t)(uint32_t)hist0 << 32) ^ ((uint64_t)o->level << 8) ^ ((uint64_t)pos_bits << 16) ^ (epochMode ? (uint64_t)1 << 24 : 0);
+    if (key == 0) key = 1;
+    if (c->proto_key != key || c->proto_ptr != c->proto.p || c->dictbuf_ptr != c->dictbuf.p) {
+        c->proto_key = 0;
+        HIPCHK(c, hipMemcpyAsync(c->dictbuf.p, o->dict, (size_t)hist0, hipMemcpyHostToDevice, st));
+        std::vector<uint8_t> proto(kc_zbetter_table_bytes(), 0);
+        if (o->level == KC_SPEED_BEST) { /* the kernel indexes the dictionary itself, per unit (bestFastEncoder.Reset) */ }
+        else if (o->level == KC_SPEED_BETTER) {
+            build_better_dict_tables(o->dict, (size_t)hist0, pos_bits, proto.data(), epochMode ? 4 : 0);
+        } else if (o->level == KC_SPEED_DEFAULT) {
+            build_dfast_dict_long(o->dict, (size_t)hist0, pos_bits, (uint32_t*)proto.data());
+            build_fast_dict_table(o->dict, (size_t)hist0, pos_bits, (uint32_t*)(proto.data() + ((size_t)4 << 17)));
+        } else build_fast_dict_table(o->dict, (size_t)hist0, pos_bits, (uint32_t*)proto.data());
+        HIPCHK(c, hipMemcpyAsync(c->proto.p, proto.data(), proto.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipStreamSynchronize(st));  // proto and woff are locals
+        c->proto_key = key;
+        c->proto_ptr = c->proto.p;
+        c->dictbuf_ptr = c->dictbuf.p;
+    } else {
+        HIPCHK(c, hipStreamSynchronize(st));  // woff is a local
+    }
+    kc_launch_prefix_units(d_src, (const uint64_t*)c->unit_off.p, (const uint64_t*)c->work_off.p, (const uint8_t*)c->dictbuf.p,
+                           (uint32_t)hist0, (uint8_t*)c->work.p, n_units, st);
+    b.src = (const uint8_t*)c->work.p;
+    b.unit_off = (const uint64_t*)c->work_off.p;
+    return KC_OK;
+}
+
+// the jobs of one WithConcurrentBlocks stream: per unit its overlap prefix and its flags
+static kc_status begin_jobs(kc_ctx* c, const Plan& pl, hipStream_t st, KcZencBufs& b) {
+    const size_t n_units = pl.n_units;
+    kc_status s;
+    if (pl.hist0) { c->err = "jobs of a WithConcurrentBlocks stream take no dictionary"; return KC_ERR_INTERNAL; }
+    if ((s = ensure(c, c->d_job_hist, n_units * 4)) || (s = ensure(c, c->d_job_flags, n_units * 4))) return s;
+    HIPCHK(c, hipMemcpyAsync(c->d_job_hist.p, c->job_hist, n_units * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->d_job_flags.p, c->job_flags, n_units * 4, hipMemcpyHostToDevice, st));
+    b.job_hist = (const uint32_t*)c->d_job_hist.p;
+    b.job_flags = (const uint32_t*)c->d_job_flags.p;
+    return KC_OK;
+}
+
+// the two parameter blocks over the context's buffers (a full-format dictionary's literal table is staged on the way)
+static kc_status begin_params(kc_ctx* c, const kc_zstd_opts* o, const Plan& pl, bool fuse_xxh, hipStream_t st, KcZencBufs& b, KcMatchParams& mp,
+                              KcEntropyParams& ep) {
+    if (o->dict_huf_len > 0) {
+        uint8_t blobh[768];
+        memcpy(blobh, o->dict_huf_val, 512);
+        memcpy(blobh + 512, o->dict_huf_nbits, 256);
+        const kc_status sh = ensure(c, c->dicthuf, 768);
+        if (sh != KC_OK) return sh;
+        HIPCHK(c, hipMemcpyAsync(c->dicthuf.p, blobh, 768, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipStreamSynchronize(st));  // blobh is a stack buffer
+        b.dict_huf = (const uint8_t*)c->dicthuf.p;
+    }
+    // raw blocks are copied once, by the compaction, from the source (KcRawDef): the entries of blocks that are not raw stay zero
+    kc_status s;
+    if ((s = ensure(c, c->rawdef, ((size_t)pl.n_blocks + 1) * sizeof(KcRawDef))) != KC_OK) return s;
+    if (fuse_xxh && (s = ensure(c, c->unit_raw, (size_t)pl.n_units * 4 + 4)) != KC_OK) return s;
+    b.unit_blk0 = (const uint32_t*)c->unit_blk0.p;
+    b.blk_start = (const uint32_t*)c->blk_start.p;
+    b.unit_flags = (const uint32_t*)c->unit_flags.p;
+    b.seqs = (uint64_t*)c->seqs.p;
+    b.aux = (uint64_t*)c->aux.p;
+    b.meta = (KcBlkMeta*)c->meta.p;
+    b.lits = (uint8_t*)c->lits.p;
+    b.stage = (uint8_t*)c->stage.p;
+    b.stage_off = (const uint64_t*)c->stage_off.p;
+    b.out_size = (uint32_t*)c->out_size.p;
+    b.xxh = (const uint64_t*)c->xxh.p;
+    b.redo = (uint32_t*)c->redo.p;
+    b.redo_blk = (uint8_t*)c->redo_blk.p;
+    b.predef = c->predef.p;
+    b.errflag = (uint32_t*)c->errflag.p;
+    b.rawdef = (KcRawDef*)c->rawdef.p;
+    b.unit_raw = (uint32_t*)c->unit_raw.p;
+    KcZencSteer cx;
+    cx.stream_mode = c->stream_mode;
+    cx.spec_w0 = c->cfg.spec_w0;
+    cx.spec_grow = c->cfg.spec_grow;
+    cx.fuse_xxh = fuse_xxh;
+    zenc_fill_params(o, pl, b, cx, mp, ep);
+    return KC_OK;
+}
+
+// the batch's flag arrays, zeroed by one launch (every DevBuf has at least 256 bytes of slack behind the size asked for); the
+// shader-clock counters when they are asked for
+static kc_status begin_clear(kc_ctx* c, const Plan& pl, bool fuse_xxh, hipStream_t st, KcMatchParams& mp, KcEntropyParams& ep) {
+    const size_t n_units = pl.n_units, nb = pl.n_blocks;
+    KcClearList cl;
+    memset(&cl, 0, sizeof(cl));
+    auto add = [&](void* q, size_t bytes) { cl.p[cl.count] = q; cl.n16[cl.count] = (bytes + 15) / 16; cl.count++; };
+    add(c->redo.p, n_units * 4);
+    add(c->redo_blk.p, nb + 1);
+    add(c->errflag.p, 64);
+    add(c->rawdef.p, (nb + 1) * sizeof(KcRawDef));
+    if (fuse_xxh) add(c->unit_raw.p, n_units * 4);
+    kc_launch_clear(cl, st);
+    if (c->cfg.k2_prof != 0) {
+        const kc_status s = ensure(c, c->prof, 48 * 8);
+        if (s != KC_OK) return s;
+        HIPCHK(c, hipMemsetAsync(c->prof.p, 0, 48 * 8, st));
+        ep.prof = (unsigned long long*)c->prof.p;
+        mp.prof = (unsigned long long*)c->prof.p + 32;
+    }
+    return KC_OK;
+}
+
+// the no-match pre-scan in front of the match finder, where zenc_run_prescan says so
+static kc_status begin_prescan(kc_ctx* c, const kc_zstd_opts* o, const Plan& pl, bool fuse_xxh, hipStream_t st, KcMatchParams& mp, KcEntropyParams& ep) {
+    const int bs = o->block_size;
+    c->prescan_ran = false;
+    if (!zenc_run_prescan(o, pl, c->cfg.zfast_prescan, zenc_tuned_form(c->cfg.zfast_variant, c->last_incompressible) == 1, fuse_xxh, c->stream_mode)) return KC_OK;
+    kc_status s;
+    if (c->probe_bs != bs || c->probe_rel.p == nullptr) {
+        std::vector<uint32_t> rel(4096);
+        uint32_t n = kc_zfast_probe_positions(bs, rel.data(), (uint32_t)rel.size());
+        if (n > rel.size()) { rel.resize(n); n = kc_zfast_probe_positions(bs, rel.data(), (uint32_t)rel.size()); }
+        if ((s = ensure(c, c->probe_rel, (size_t)n * 4 + 16)) != KC_OK) return s;
+        HIPCHK(c, hipMemcpyAsync(c->probe_rel.p, rel.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipStreamSynchronize(st));  // rel is a local
+        c->probe_bs = bs;
+        c->probe_n = n;
+    }
+    if ((s = ensure(c, c->unit_done, (size_t)pl.n_units * 4 + 16)) != KC_OK) return s;
+    const KcPrescanParams pp = zenc_prescan_params(o, pl, mp, ep, (const uint32_t*)c->probe_rel.p, c->probe_n, (uint32_t*)c->unit_done.p);
+    kc_launch_zfast_prescan(pp, st);
+    mp.unit_done = pp.unit_done;
+    ep.unit_done = pp.unit_done;
+    c->prescan_ran = true;
+    return KC_OK;
+}
+
+// the source is still arriving: per chunk, checksum + match finder + entropy stage + compaction on the chunk's stream behind its H2D copy
+static kc_status begin_feed(kc_ctx* c, const kc_zstd_opts* o, const Plan& pl, const uint8_t* d_src, uint8_t* d_dst, ChunkFeed* feed, hipStream_t st,
+                            const KcMatchParams& mp, const KcEntropyParams& ep) {
+    const uint32_t n_units = pl.n_units;
+    kc_status s;
+    if (pl.hist0) { c->err = "chunk feed does not take dictionaries"; return KC_ERR_INTERNAL; }
+    HIPCHK(c, hipEventRecord(c->ev[1], st));
+    if ((s = prepare_tables(c, mp, n_units, st, o->level)) != KC_OK) return s;
+    const bool feed_lds = zfast_use_lds(c, mp, n_units, o->level);
+    HIPCHK(c, hipEventRecord(c->ev[6], st));  // everything the chunk kernels need from this stream (offset arrays, tables)
+    const size_t nchunk = feed->cut.size() - 1;
+    for (size_t k = 0; k < nchunk; k++) {
+        if (!feed->wait_recorded(k)) { c->err = "host pipeline: staging failed"; return KC_ERR_HIP; }
+        hipStream_t sk = feed->streams[k % feed->streams.size()];
+        const uint32_t u0 = feed->cut[k], nk = feed->cut[k + 1] - feed->cut[k];
+        HIPCHK(c, hipStreamWaitEvent(sk, c->ev[6], 0));
+        HIPCHK(c, hipStreamWaitEvent(sk, feed->landed[k], 0));
+        if (o->crc) kc_launch_xxh64(d_src, (const uint64_t*)c->unit_off.p + u0, nk, (uint64_t*)c->xxh.p + u0, sk);
+        KcMatchParams mk = mp;
+        mk.unit_base = u0;
+        launch_match_kernel(c, mk, u0, nk, sk, o->level, feed_lds);
+        KcEntropyParams ek = ep;
+        ek.unit_base = u0;
+        kc_launch_zstd_entropy(ek, nk, sk);
+        feed->loc_off = (uint64_t*)c->out_off.p;
+        kc_launch_scan_sizes((const uint32_t*)c->out_size.p + u0, nk, feed->loc_off + u0 + k, sk);
+        kc_launch_compact((const uint8_t*)c->stage.p, (const uint64_t*)c->stage_off.p + u0, (const uint32_t*)c->out_size.p + u0,
+                          feed->loc_off + u0 + k, d_dst + pl.stage_off[u0], nk, sk, ep.src, ep.unit_off + u0, ep.unit_blk0 + u0, ep.rawdef);
+        HIPCHK(c, hipEventRecord(feed->done[k], sk));
+    }
+    for (size_t k = 0; k < nchunk; k++) HIPCHK(c, hipStreamWaitEvent(st, feed->done[k], 0));
+    return KC_OK;
 }
 
 kc_status batch_begin(kc_ctx* c, const kc_zstd_opts* o, const uint8_t* d_src_base, const uint64_t* unit_off, uint32_t n_units,
                       uint8_t* d_dst, uint64_t dst_cap, ChunkFeed* feed) {
     hipStream_t st = c->stream;
     if (c->pend) { c->err = "a batch is already in flight on this context"; return KC_ERR_BAD_ARG; }
-    const int bs = o->block_size;
     Plan& pl = c->plan;
-    pl.n_units = n_units;
-    pl.blk0.resize(n_units + 1);
-    pl.stage_off.resize(n_units + 1);
-    pl.rel_off.resize(n_units + 1);
-    uint64_t so = 0;
-    uint32_t nb = 0;
-    const bool irregular = c->cuts != nullptr;
-    pl.blk_start.clear();
-    pl.unit_flags.clear();
-    for (uint32_t i = 0; i < n_units; i++) {
-        const uint64_t len = unit_off[i + 1] - unit_off[i];
-        pl.blk0[i] = nb;
-        pl.stage_off[i] = so;
-        pl.rel_off[i] = unit_off[i] - unit_off[0];
-        uint32_t ub = (uint32_t)((len - (c->job_hist ? c->job_hist[i] : 0) + bs - 1) / bs);  // (a job's overlap prefix is history, not blocks)
-        if (irregular) {
-            const uint64_t* cp = c->cuts + c->cut_off[c->cut_unit0 + i];
-            const uint64_t nc = c->cut_off[c->cut_unit0 + i + 1] - c->cut_off[c->cut_unit0 + i];
-            uint32_t fl = 0;
-            ub = plan_stream_blocks((uint64_t)bs, len, cp, nc, &pl.blk_start, &fl);
-            pl.unit_flags.push_back(fl);
-        }
-        nb += ub;
-        // every block costs a 3-byte header: Flush points add blocks that MaxEncodedSize(len) does not count
-        so += ((uint64_t)kc_zstd_max_encoded_size(o, (int64_t)len) + (irregular ? 3ull * (c->cut_off[c->cut_unit0 + i + 1] - c->cut_off[c->cut_unit0 + i]) + 3ull : 0ull) + 15) & ~(uint64_t)15;
-    }
-    pl.blk0[n_units] = nb;
-    pl.stage_off[n_units] = so;
-    pl.rel_off[n_units] = unit_off[n_units] - unit_off[0];
-    pl.n_blocks = nb;
-    pl.seq_stride = (uint32_t)(bs / 4 + 8);
-    pl.lit_stride = (uint32_t)(bs + 64);
-    if (so > dst_cap) { c->err = "dst_cap smaller than the sum of MaxEncodedSize(unit)"; return KC_ERR_DST_TOO_SMALL; }
-
-    kc_status s;
-    if ((s = ensure(c, c->unit_off, (n_units + 1) * 8)) || (s = ensure(c, c->unit_blk0, (n_units + 1) * 4)) ||
-        (s = ensure(c, c->stage_off, (n_units + 1) * 8)) || (s = ensure(c, c->out_off, (n_units + 1 + (feed ? feed->cut.size() : 0)) * 8)) ||
-        (s = ensure(c, c->seqs, (size_t)nb * pl.seq_stride * 8)) || (s = ensure(c, c->aux, (size_t)nb * pl.seq_stride * 8)) ||
-        (s = ensure(c, c->lits, (size_t)nb * pl.lit_stride)) || (s = ensure(c, c->meta, (size_t)nb * sizeof(KcBlkMeta))) ||
-        (s = ensure(c, c->stage, so + 64)) || (s = ensure(c, c->out_size, (size_t)n_units * 4)) ||
-        (s = ensure(c, c->xxh, (size_t)n_units * 8)) || (s = ensure(c, c->redo, (size_t)n_units * 4)) ||
-        (s = ensure(c, c->redo_blk, (size_t)nb + 1)) || (s = ensure(c, c->pop_blk, (size_t)nb + 1)) || (s = ensure(c, c->unit_list, (size_t)n_units * 4)) ||
-        (s = ensure(c, c->predef, kc_fse_predef_bytes())) || (s = ensure(c, c->errflag, 64)))
-        return s;
-    if (!c->predef_ready) {
-        kc_launch_fse_predef_init(c->predef.p, st);
-        c->predef_ready = true;
-    }
-    if (irregular) {
-        if ((s = ensure(c, c->blk_start, ((size_t)nb + 1) * 4)) || (s = ensure(c, c->unit_flags, (size_t)n_units * 4))) return s;
-        if (nb) HIPCHK(c, hipMemcpyAsync(c->blk_start.p, pl.blk_start.data(), (size_t)nb * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->unit_flags.p, pl.unit_flags.data(), (size_t)n_units * 4, hipMemcpyHostToDevice, st));
-    }
-    {   // the layout arrays: batches of equal-sized units repeat them exactly (every step of a fixed-size workload), and a copy from
-        // pageable memory stalls the host for tens of microseconds each — upload only what differs from what the device holds
-        auto same = [](const std::vector<uint8_t>& held, const void* p, size_t n, const void* dev, const void* held_dev) {
-            return dev == held_dev && held.size() == n && memcmp(held.data(), p, n) == 0;
-        };
-        auto keep = [](std::vector<uint8_t>& held, const void* p, size_t n) { held.assign((const uint8_t*)p, (const uint8_t*)p + n); };
-        const size_t n8 = (size_t)(n_units + 1) * 8, n4 = (size_t)(n_units + 1) * 4;
-        if (!same(c->up_unit_off, pl.rel_off.data(), n8, c->unit_off.p, c->up_ptr[0])) {
-            HIPCHK(c, hipMemcpyAsync(c->unit_off.p, pl.rel_off.data(), n8, hipMemcpyHostToDevice, st));
-            keep(c->up_unit_off, pl.rel_off.data(), n8);
-            c->up_ptr[0] = c->unit_off.p;
-        }
-        if (!same(c->up_blk0, pl.blk0.data(), n4, c->unit_blk0.p, c->up_ptr[1])) {
-            HIPCHK(c, hipMemcpyAsync(c->unit_blk0.p, pl.blk0.data(), n4, hipMemcpyHostToDevice, st));
-            keep(c->up_blk0, pl.blk0.data(), n4);
-            c->up_ptr[1] = c->unit_blk0.p;
-        }
-        if (!same(c->up_stage_off, pl.stage_off.data(), n8, c->stage_off.p, c->up_ptr[2])) {
-            HIPCHK(c, hipMemcpyAsync(c->stage_off.p, pl.stage_off.data(), n8, hipMemcpyHostToDevice, st));
-            keep(c->up_stage_off, pl.stage_off.data(), n8);
-            c->up_ptr[2] = c->stage_off.p;
-        }
-    }
-    // (the flag arrays of the batch are zeroed by one launch further down: kc_launch_clear)
-
+    zenc_plan(o, unit_off, n_units, c->job_hist, KcZencCuts{c->cut_off, c->cuts, c->cut_unit0}, pl);
+    if (pl.need > dst_cap) { c->err = "dst_cap smaller than the sum of MaxEncodedSize(unit)"; return KC_ERR_DST_TOO_SMALL; }
+    const bool fuse_xxh = zenc_fuse_xxh(o, pl, c->cfg.fuse_raw_xxh != 0, c->job_hist != nullptr, feed != nullptr);
     const uint8_t* d_src = d_src_base + unit_off[0];
-    // ---- dictionary (raw content, WithEncoderDictRaw): history = dict || unit (enc_base.go:189-198) ----
-    const bool useDict = o->dict != nullptr && o->dict_len > 0;
-    const int hist0 = useDict ? (int)o->dict_len : 0;
-    uint64_t maxLen = 16;
-    for (uint32_t i = 0; i < n_units; i++) maxLen = std::max<uint64_t>(maxLen, unit_off[i + 1] - unit_off[i]);
-    pl.max_unit_bytes = maxLen;
-    int pos_bits = 1;
-    while (((uint64_t)1 << pos_bits) <= (uint64_t)hist0 + maxLen + 2) pos_bits++;
-    // the packed sequences keep offset + 3 in 24 bits: fine for the default windows (4 / 8 MiB) and for any unit below 16 MiB
-    if (std::min<uint64_t>((uint64_t)o->window_size, (uint64_t)hist0 + maxLen) + 3 > 0xFFFFFFull) {
+    kc_status s;
+    if ((s = begin_reserve(c, o, pl, feed)) != KC_OK) return s;
+    if ((s = begin_upload(c, pl, st)) != KC_OK) return s;
+    if (!zenc_offsets_fit(o, pl)) {
         c->err = "window above 8 MiB with units above 16 MiB: offsets beyond the device path's 24-bit sequence field";
         return KC_ERR_UNSUPPORTED;
     }
-    const uint8_t* k_src = d_src;               // what the match finder / entropy kernels read
-    const uint64_t* k_off = (const uint64_t*)c->unit_off.p;
-    if (useDict) {
-        std::vector<uint64_t> woff(n_units + 1);
-        for (uint32_t i = 0; i <= n_units; i++) woff[i] = pl.rel_off[i] + (uint64_t)i * (uint64_t)hist0;
-        if ((s = ensure(c, c->work, woff[n_units] + 64)) || (s = ensure(c, c->work_off, (n_units + 1) * 8)) ||
-            (s = ensure(c, c->dictbuf, (size_t)hist0 + 64)) || (s = ensure(c, c->proto, kc_zbetter_table_bytes())))
-            return s;
-        HIPCHK(c, hipMemcpyAsync(c->work_off.p, woff.data(), (n_units + 1) * 8, hipMemcpyHostToDevice, st));
-        // The dictionary's content and its pristine tables (betterFastEncoderDict.Reset, enc_better.go:1114-1183, in the device entry
-        // format) are the same from batch to batch: rebuilt and uploaded only when the dictionary, the level, the position width or the
-        // stamp mode changed (round 6: the rolling host pipeline runs a batch per 256 MiB — 4 MiB of host table building, two uploads
-        // and a stream synchronisation per batch before).
-        const bool epochMode = better_epoch_mode(c, o->level, pos_bits, hist0);
-        uint64_t key = 0xcbf29ce484222325ULL;
-        for (int i = 0; i < hist0; i++) key = (key ^ o->dict[i]) * 0x100000001b3ULL;
-        key ^= ((uint64_t)(uint32_t)hist0 << 32) ^ ((uint64_t)o->level << 8) ^ ((uint64_t)pos_bits << 16) ^ (epochMode ? (uint64_t)1 << 24 : 0);
-        if (key == 0) key = 1;
-        const size_t tbz = kc_zbetter_table_bytes();
-        if (c->proto_key != key || c->proto_ptr != c->proto.p || c->dictbuf_ptr != c->dictbuf.p) {
-            c->proto_key = 0;
-            HIPCHK(c, hipMemcpyAsync(c->dictbuf.p, o->dict, (size_t)hist0, hipMemcpyHostToDevice, st));
-            std::vector<uint8_t> proto(tbz, 0);
-            if (o->level == KC_SPEED_BEST) { /* the kernel indexes the dictionary itself, per unit (bestFastEncoder.Reset) */ }
-            else if (o->level == KC_SPEED_BETTER) {
-                build_better_dict_tables(o->dict, (size_t)hist0, pos_bits, proto.data(), epochMode ? 4 : 0);
-            } else if (o->level == KC_SPEED_DEFAULT) {
-                build_dfast_dict_long(o->dict, (size_t)hist0, pos_bits, (uint32_t*)proto.data());
-                build_fast_dict_table(o->dict, (size_t)hist0, pos_bits, (uint32_t*)(proto.data() + ((size_t)4 << 17)));
-            } else build_fast_dict_table(o->dict, (size_t)hist0, pos_bits, (uint32_t*)proto.data());
-            HIPCHK(c, hipMemcpyAsync(c->proto.p, proto.data(), proto.size(), hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipStreamSynchronize(st));  // proto and woff are locals
-            c->proto_key = key;
-            c->proto_ptr = c->proto.p;
-            c->dictbuf_ptr = c->dictbuf.p;
-        } else {
-            HIPCHK(c, hipStreamSynchronize(st));  // woff is a local
-        }
-        kc_launch_prefix_units(d_src, (const uint64_t*)c->unit_off.p, (const uint64_t*)c->work_off.p, (const uint8_t*)c->dictbuf.p,
-                               (uint32_t)hist0, (uint8_t*)c->work.p, n_units, st);
-        k_src = (const uint8_t*)c->work.p;
-        k_off = (const uint64_t*)c->work_off.p;
-    }
-    if (c->job_hist) {
-        if (useDict) { c->err = "jobs of a WithConcurrentBlocks stream take no dictionary"; return KC_ERR_INTERNAL; }
-        if ((s = ensure(c, c->d_job_hist, (size_t)n_units * 4)) || (s = ensure(c, c->d_job_flags, (size_t)n_units * 4))) return s;
-        HIPCHK(c, hipMemcpyAsync(c->d_job_hist.p, c->job_hist, (size_t)n_units * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(c->d_job_flags.p, c->job_flags, (size_t)n_units * 4, hipMemcpyHostToDevice, st));
-    }
+    KcZencBufs b;
+    b.src = d_src;  // what the match finder / entropy kernels read
+    b.unit_off = (const uint64_t*)c->unit_off.p;
+    if (pl.hist0 && (s = begin_dictionary(c, o, pl, d_src, st, b)) != KC_OK) return s;
+    if (c->job_hist && (s = begin_jobs(c, pl, st, b)) != KC_OK) return s;
     KcMatchParams mp;
-    memset(&mp, 0, sizeof(mp));
-    mp.unit_hist = c->job_hist ? (const uint32_t*)c->d_job_hist.p : nullptr;
-    mp.job_flags = c->job_hist ? (const uint32_t*)c->d_job_flags.p : nullptr;
-    mp.src = k_src;
-    mp.src_end = k_src + (useDict ? pl.rel_off[n_units] + (uint64_t)n_units * (uint64_t)hist0 : pl.rel_off[n_units]);
-    mp.unit_off = k_off;
-    mp.hist0 = hist0;
-    mp.pos_bits = pos_bits;
-    mp.stream_mode = c->stream_mode;
-    mp.rep1 = (int32_t)o->dict_offsets[0];
-    mp.rep2 = (int32_t)o->dict_offsets[1];
-    mp.rep3 = (int32_t)o->dict_offsets[2];
-    if (mp.rep1 <= 0 || mp.rep2 <= 0 || mp.rep3 <= 0) { mp.rep1 = 1; mp.rep2 = 4; mp.rep3 = 8; }  // opts not initialised through kc_zstd_opts_default
-    mp.unit_blk0 = (const uint32_t*)c->unit_blk0.p;
-    mp.seqs = (uint64_t*)c->seqs.p;
-    mp.meta = (KcBlkMeta*)c->meta.p;
-    mp.pop_blk = nullptr;
-    mp.unit_list = nullptr;
-    mp.blk_start = irregular ? (const uint32_t*)c->blk_start.p : nullptr;
-    mp.unit_flags = irregular ? (const uint32_t*)c->unit_flags.p : nullptr;
-    mp.seq_stride = pl.seq_stride;
-    mp.block_size = bs;
-    mp.max_match_off = o->window_size;
-    // SpeedDefault, round 2 (ms per launch): at 4 GiB (32768 units: DRAM-transaction bound, wasted probes cost) width 2 / 3 / 4 then doubling
-    // 265.9 / 266.7 / 274.0, 2 then +1 264.1; at 2 GiB (latency bound) 163.6 / - / 155.4, fixed 1: 285.5.  The BASELINE size is 4 GiB.
-    // SpeedBetterCompression (1 GiB = 8192 units: latency-bound, wide speculation pays): width 1 / 2 / 4 then doubling 98.6 / 91.5 / 86.0,
-    // fixed 4: 101.4, fixed 8: 80.4 ms with 8 lanes per unit; 16 lanes per unit, fixed 16: 61.1 ms (one probe per round, round 1: 181 ms)
-    mp.spec_w0 = c->cfg.spec_w0 >= 0 ? (int)c->cfg.spec_w0 : (o->level == KC_SPEED_DEFAULT ? 2 : (o->level == KC_SPEED_BETTER ? 16 : 1));
-    // measured on C2 (ms per 4 GiB): width 1 then +1 per miss 137, fixed 2 136.5, 1 then doubling 140, fixed 1 167, fixed 4 157
-    mp.spec_grow = c->cfg.spec_grow >= 0 ? (int)c->cfg.spec_grow : (o->level == KC_SPEED_FASTEST ? 1 : (o->level == KC_SPEED_BETTER ? 0 : 2));
-    if (mp.spec_w0 < 1) mp.spec_w0 = 1;
-    if (mp.spec_w0 > 64) mp.spec_w0 = 64;  // the kernels clamp to their group size
-
     KcEntropyParams ep;
-    memset(&ep, 0, sizeof(ep));
-    ep.unit_hist = mp.unit_hist;
-    ep.job_flags = mp.job_flags;
-    ep.src = k_src;
-    ep.unit_off = k_off;
-    ep.hist0 = hist0;
-    ep.stream_mode = c->stream_mode;
-    ep.stream_sync = o->concurrent == 1;
-    ep.dict_huf = nullptr;
-    ep.dict_huf_len = 0;
-    ep.dict_huf_log = 0;
-    if (o->dict_huf_len > 0) {  // dictionary literal table -> prevTable of every unit's first block
-        uint8_t blobh[768];
-        memcpy(blobh, o->dict_huf_val, 512);
-        memcpy(blobh + 512, o->dict_huf_nbits, 256);
-        if ((s = ensure(c, c->dicthuf, 768))) return s;
-        HIPCHK(c, hipMemcpyAsync(c->dicthuf.p, blobh, 768, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipStreamSynchronize(st));  // blobh is a stack buffer
-        ep.dict_huf = (const uint8_t*)c->dicthuf.p;
-        ep.dict_huf_len = o->dict_huf_len;
-        ep.dict_huf_log = o->dict_huf_log;
-    }
-    ep.unit_blk0 = mp.unit_blk0;
-    ep.seqs = mp.seqs;
-    ep.meta = mp.meta;
-    ep.lits = (uint8_t*)c->lits.p;
-    ep.aux = (uint64_t*)c->aux.p;
-    ep.stage = (uint8_t*)c->stage.p;
-    ep.stage_off = (const uint64_t*)c->stage_off.p;
-    ep.out_size = (uint32_t*)c->out_size.p;
-    ep.xxh = (const uint64_t*)c->xxh.p;
-    ep.redo_mask = (uint32_t*)c->redo.p;
-    ep.redo_blk = (uint8_t*)c->redo_blk.p;
-    ep.blk_start = mp.blk_start;
-    ep.unit_flags = mp.unit_flags;
-    ep.unit_list = nullptr;
-    ep.predef = c->predef.p;
-    ep.seq_stride = pl.seq_stride;
-    ep.lit_stride = pl.lit_stride;
-    ep.block_size = bs;
-    ep.window_size = o->window_size;
-    ep.crc = o->crc;
-    ep.single = o->single;
-    ep.no_entropy = o->no_entropy;
-    ep.all_lit_entropy = o->all_lit_entropy;
-    ep.full_zero = o->full_zero;
-    ep.dict_id = o->dict_id;
-    ep.err_flag = (uint32_t*)c->errflag.p;
-    // raw blocks are copied once, by the compaction, from the source (KcRawDef): the entries of blocks that are not raw stay zero
-    if ((s = ensure(c, c->rawdef, ((size_t)nb + 1) * sizeof(KcRawDef))) != KC_OK) return s;
-    ep.rawdef = (KcRawDef*)c->rawdef.p;
-    // The checksum moves behind the entropy stage (kc_xxh64_fin_kernel) where the batch has a regular block grid and no history in
-    // front of its units: frames that turn out to be raw blocks only then get their payload copied by the pass that hashes it.
-    const bool fuse_xxh = c->cfg.fuse_raw_xxh != 0 && o->crc && !c->job_hist && !useDict && hist0 == 0 && !irregular && (bs % 256) == 0 && feed == nullptr;
-    ep.unit_raw = nullptr;
-    if (fuse_xxh) {
-        if ((s = ensure(c, c->unit_raw, (size_t)n_units * 4 + 4)) != KC_OK) return s;
-        ep.unit_raw = (uint32_t*)c->unit_raw.p;
-        ep.xxh = nullptr;
-    }
-    {   // the batch's flag arrays, zeroed by one launch (every DevBuf has at least 256 bytes of slack behind the size asked for)
-        KcClearList cl;
-        memset(&cl, 0, sizeof(cl));
-        auto add = [&](void* q, size_t bytes) { cl.p[cl.count] = q; cl.n16[cl.count] = (bytes + 15) / 16; cl.count++; };
-        add(c->redo.p, (size_t)n_units * 4);
-        add(c->redo_blk.p, (size_t)nb + 1);
-        add(c->errflag.p, 64);
-        add(c->rawdef.p, ((size_t)nb + 1) * sizeof(KcRawDef));
-        if (fuse_xxh) add(c->unit_raw.p, (size_t)n_units * 4);
-        kc_launch_clear(cl, st);
-    }
-    ep.prof = nullptr;
-    const bool k2prof = c->cfg.k2_prof != 0;
-    if (k2prof) {
-        if ((s = ensure(c, c->prof, 48 * 8)) != KC_OK) return s;
-        HIPCHK(c, hipMemsetAsync(c->prof.p, 0, 48 * 8, st));
-        ep.prof = (unsigned long long*)c->prof.p;
-        mp.prof = (unsigned long long*)c->prof.p + 32;
-    }
-
+    if ((s = begin_params(c, o, pl, fuse_xxh, st, b, mp, ep)) != KC_OK) return s;
+    if ((s = begin_clear(c, pl, fuse_xxh, st, mp, ep)) != KC_OK) return s;
     if (c->chain_after) HIPCHK(c, hipStreamWaitEvent(st, c->chain_after->ev[2], 0));  // pipelined contexts: one match finder at a time
     HIPCHK(c, hipEventRecord(c->ev[0], st));
-    // The no-match pre-scan (kc_zstd_prescan.hip): SpeedFastest EncodeAll batches whose frames take the deferred-payload path
-    // (fuse_xxh: checksum on, regular block grid, no dictionary / job prefix / chunk feed), literal-only blocks going out raw
-    // (rawAllLits, the default below SpeedBetterCompression).  On by option, or per batch when the context's previous batch did not
-    // compress (the same signal that picks the match finder's form for such input).
-    c->prescan_ran = false;
-    {
-        const bool tuned_now = c->cfg.zfast_variant < 0 ? c->last_incompressible : c->cfg.zfast_variant == 1;
-        const bool want = c->cfg.zfast_prescan > 0 || (c->cfg.zfast_prescan < 0 && tuned_now);
-        if (want && o->level == KC_SPEED_FASTEST && fuse_xxh && !c->stream_mode && !o->all_lit_entropy && bs >= 16 && n_units > 0) {
-            if (c->probe_bs != bs || c->probe_rel.p == nullptr) {
-                std::vector<uint32_t> rel(4096);
-                uint32_t n = kc_zfast_probe_positions(bs, rel.data(), (uint32_t)rel.size());
-                if (n > rel.size()) { rel.resize(n); n = kc_zfast_probe_positions(bs, rel.data(), (uint32_t)rel.size()); }
-                if ((s = ensure(c, c->probe_rel, (size_t)n * 4 + 16)) != KC_OK) return s;
-                HIPCHK(c, hipMemcpyAsync(c->probe_rel.p, rel.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-                HIPCHK(c, hipStreamSynchronize(st));  // rel is a local
-                c->probe_bs = bs;
-                c->probe_n = n;
-            }
-            if ((s = ensure(c, c->unit_done, (size_t)n_units * 4 + 16)) != KC_OK) return s;
-            KcPrescanParams pp;
-            memset(&pp, 0, sizeof(pp));
-            pp.src = k_src;
-            pp.unit_off = k_off;
-            pp.unit_blk0 = mp.unit_blk0;
-            pp.n_units = n_units;
-            pp.block_size = bs;
-            pp.probe_rel = (const uint32_t*)c->probe_rel.p;
-            pp.n_probe = c->probe_n;
-            pp.rep1 = mp.rep1;
-            pp.rep2 = mp.rep2;
-            pp.meta = mp.meta;
-            pp.unit_done = (uint32_t*)c->unit_done.p;
-            pp.stage = ep.stage;
-            pp.stage_off = ep.stage_off;
-            pp.out_size = ep.out_size;
-            pp.rawdef = ep.rawdef;
-            pp.unit_raw = ep.unit_raw;
-            pp.window_size = o->window_size;
-            pp.crc = o->crc;
-            pp.single = o->single;
-            pp.dict_id = o->dict_id;
-            kc_launch_zfast_prescan(pp, st);
-            mp.unit_done = pp.unit_done;
-            ep.unit_done = pp.unit_done;
-            c->prescan_ran = true;
-        }
-    }
+    if ((s = begin_prescan(c, o, pl, fuse_xxh, st, mp, ep)) != KC_OK) return s;
     mp.unit_base = 0;
     ep.unit_base = 0;
     if (feed == nullptr) {
         if (o->crc && !c->job_hist && !fuse_xxh) kc_launch_xxh64(d_src, (const uint64_t*)c->unit_off.p, n_units, (uint64_t*)c->xxh.p, st);  // (a job stream's checksum is the host's)
         HIPCHK(c, hipEventRecord(c->ev[1], st));
-        if ((s = launch_match(c, mp, unit_off, n_units, n_units, bs, st, o->level)) != KC_OK) return s;
-    } else {
-        // the source is still arriving: per chunk, checksum + match finder on the chunk's stream behind its H2D copy
-        if (useDict) { c->err = "chunk feed does not take dictionaries"; return KC_ERR_INTERNAL; }
-        HIPCHK(c, hipEventRecord(c->ev[1], st));
-        if ((s = prepare_tables(c, mp, n_units, st, o->level)) != KC_OK) return s;
-        const bool feed_lds = zfast_use_lds(c, mp, n_units, o->level);
-        HIPCHK(c, hipEventRecord(c->ev[6], st));  // everything the chunk kernels need from this stream (offset arrays, tables)
-        const size_t nchunk = feed->cut.size() - 1;
-        for (size_t k = 0; k < nchunk; k++) {
-            if (!feed->wait_recorded(k)) { c->err = "host pipeline: staging failed"; return KC_ERR_HIP; }
-            hipStream_t sk = feed->streams[k % feed->streams.size()];
-            const uint32_t u0 = feed->cut[k], nk = feed->cut[k + 1] - feed->cut[k];
-            HIPCHK(c, hipStreamWaitEvent(sk, c->ev[6], 0));
-            HIPCHK(c, hipStreamWaitEvent(sk, feed->landed[k], 0));
-            if (o->crc) kc_launch_xxh64(d_src, (const uint64_t*)c->unit_off.p + u0, nk, (uint64_t*)c->xxh.p + u0, sk);
-            KcMatchParams mk = mp;
-            mk.unit_base = u0;
-            launch_match_kernel(c, mk, u0, nk, sk, o->level, feed_lds);
-            KcEntropyParams ek = ep;
-            ek.unit_base = u0;
-            kc_launch_zstd_entropy(ek, nk, sk);
-            feed->loc_off = (uint64_t*)c->out_off.p;
-            kc_launch_scan_sizes((const uint32_t*)c->out_size.p + u0, nk, feed->loc_off + u0 + k, sk);
-            kc_launch_compact((const uint8_t*)c->stage.p, (const uint64_t*)c->stage_off.p + u0, (const uint32_t*)c->out_size.p + u0,
-                              feed->loc_off + u0 + k, d_dst + pl.stage_off[u0], nk, sk, ep.src, ep.unit_off + u0, ep.unit_blk0 + u0, ep.rawdef);
-            HIPCHK(c, hipEventRecord(feed->done[k], sk));
-        }
-        for (size_t k = 0; k < nchunk; k++) HIPCHK(c, hipStreamWaitEvent(st, feed->done[k], 0));
-    }
+        if ((s = launch_match(c, mp, unit_off, n_units, n_units, o->block_size, st, o->level)) != KC_OK) return s;
+    } else if ((s = begin_feed(c, o, pl, d_src, d_dst, feed, st, mp, ep)) != KC_OK) return s;
     HIPCHK(c, hipEventRecord(c->ev[2], st));
     HIPCHK(c, hipGetLastError());
     Pending* P = new Pending();
@@ -676,12 +568,21 @@ kc_status batch_begin(kc_ctx* c, const kc_zstd_opts* o, const uint8_t* d_src_bas
     P->unit_off.assign(unit_off, unit_off + n_units + 1);
     P->n_units = n_units;
     P->d_dst = d_dst;
-    P->need = pl.stage_off[n_units];
+    P->need = pl.need;
     P->fed = feed != nullptr;
-    P->bs = bs;
-    P->k2prof = k2prof;
+    P->bs = o->block_size;
+    P->k2prof = c->cfg.k2_prof != 0;
     c->pend = P;
     return KC_OK;
+}
+
+// the device's error flag as read back behind a batch
+static kc_status device_verdict(kc_ctx* c, const uint32_t* errv) {
+    if (errv[0] == 0) return KC_OK;
+    char b[96];
+    snprintf(b, sizeof(b), "device invariant violated (code %u)", errv[0]);
+    c->err = b;
+    return errv[0] == 100u ? KC_ERR_UNSUPPORTED : KC_ERR_INTERNAL;
 }
 
 kc_status batch_end(kc_ctx* c, uint64_t* out_off_host, uint64_t* produced) {
@@ -712,20 +613,7 @@ kc_status batch_end(kc_ctx* c, uint64_t* out_off_host, uint64_t* produced) {
     auto finish_pass = [&]() -> kc_status {
         kc_launch_scan_sizes((const uint32_t*)c->out_size.p, n_units, (uint64_t*)c->out_off.p, st);
         if (ep.unit_raw != nullptr) {  // the checksum, and with it the payload of the frames that are raw blocks only
-            KcXxhFinParams xf;
-            xf.src = ep.src;
-            xf.unit_off = ep.unit_off;
-            xf.n_units = n_units;
-            xf.stage = (uint8_t*)c->stage.p;
-            xf.stage_off = (const uint64_t*)c->stage_off.p;
-            xf.out_size = (const uint32_t*)c->out_size.p;
-            xf.out_off = (const uint64_t*)c->out_off.p;
-            xf.dst = d_dst;
-            xf.unit_raw = ep.unit_raw;
-            xf.rawdef = ep.rawdef;
-            xf.unit_blk0 = ep.unit_blk0;
-            xf.xxh_out = (uint64_t*)c->xxh.p;
-            xf.mode = (int32_t)c->cfg.xxh_fin_mode;
+            const KcXxhFinParams xf = zenc_xxh_fin_params(ep, n_units, (const uint64_t*)c->out_off.p, d_dst, (uint64_t*)c->xxh.p, (int32_t)c->cfg.xxh_fin_mode);
             kc_launch_xxh64_fin(xf, st);
         }
         kc_launch_compact((const uint8_t*)c->stage.p, (const uint64_t*)c->stage_off.p, (const uint32_t*)c->out_size.p,
@@ -736,15 +624,12 @@ kc_status batch_end(kc_ctx* c, uint64_t* out_off_host, uint64_t* produced) {
     HIPCHK(c, hipEventRecord(c->ev[4], st));
     if ((s = finish_pass()) != KC_OK) return s;
     HIPCHK(c, hipEventRecord(c->ev[5], st));
-    // Speculation check: a block that fell back to raw only after entropy coding (blockenc.go:811-817)
-    // pops the repeat offsets; if the following block was parsed with the un-popped offsets the unit is
-    // re-run with that verdict forced.  Rare (needs a compressible-looking block that ends larger than raw).
+    // Speculation check (the rule: kc_zenc_host.h).  Rare: needs a compressible-looking block that ends larger than raw.
     uint32_t redo_units = 0;
     {
         const Plan& pl = c->plan;  // this batch's layout (one batch in flight per context)
         const uint32_t nb = pl.n_blocks;
-        uint32_t maxBlocks = 1;
-        for (uint32_t i = 0; i < n_units; i++) maxBlocks = std::max(maxBlocks, pl.blk0[i + 1] - pl.blk0[i]);
+        const uint32_t max_passes = zenc_redo_max_passes(pl);
         std::vector<uint32_t> redo(n_units), list;
         std::vector<uint8_t> redo_blk, pop_blk;
         uint32_t errv[16];
@@ -761,24 +646,14 @@ kc_status batch_end(kc_ctx* c, uint64_t* out_off_host, uint64_t* produced) {
                 c->last_prescan_units = 0;
                 for (uint32_t v : doneh) c->last_prescan_units += v != 0u;
             }
-            if (errv[0] != 0) {
-                char b[96];
-                snprintf(b, sizeof(b), "device invariant violated (code %u)", errv[0]);
-                c->err = b;
-                return errv[0] == 100u ? KC_ERR_UNSUPPORTED : KC_ERR_INTERNAL;
-            }
-            list.clear();
-            for (uint32_t i = 0; i < n_units; i++)
-                if (redo[i]) list.push_back(i);
+            if ((s = device_verdict(c, errv)) != KC_OK) return s;
+            zenc_redo_units(redo.data(), n_units, list);
             if (list.empty()) break;
-            if (iter > maxBlocks + 1) { c->err = "speculation re-run did not converge"; return KC_ERR_INTERNAL; }  // every pass settles one more block per unit
+            if (iter > max_passes) { c->err = "speculation re-run did not converge"; return KC_ERR_INTERNAL; }
             redo_blk.resize(nb);
-            if (pop_blk.empty()) pop_blk.assign(nb, 0);
             HIPCHK(c, hipMemcpyAsync(redo_blk.data(), c->redo_blk.p, nb, hipMemcpyDeviceToHost, st));
             HIPCHK(c, hipStreamSynchronize(st));
-            for (uint32_t i : list)
-                for (uint32_t b = pl.blk0[i]; b < pl.blk0[i + 1]; b++)
-                    if (redo_blk[b]) { pop_blk[b] = 1; break; }  // only the lowest flagged block is trustworthy
+            zenc_redo_mark(pl, list, redo_blk.data(), pop_blk);
             redo_units += (uint32_t)list.size();
             HIPCHK(c, hipMemcpyAsync(c->pop_blk.p, pop_blk.data(), nb, hipMemcpyHostToDevice, st));
             HIPCHK(c, hipMemcpyAsync(c->unit_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, st));
@@ -860,19 +735,6 @@ kc_status batch_end(kc_ctx* c, uint64_t* out_off_host, uint64_t* produced) {
     return KC_OK;
 }
 
-// A batch is bounded by its input bytes AND by the device scratch it needs: tables are per unit, sequences / literals /
-// staging are per block at a fixed stride whatever the block's actual length, so many small units need far more than the
-// "~6x input" of full-size units (1M x 4 KiB units at SpeedDefault would ask for hundreds of GiB in one batch).
-uint64_t zstd_unit_scratch(const kc_zstd_opts* o, uint64_t len, uint64_t n_cuts) {
-    const uint64_t bsz = (uint64_t)o->block_size;
-    const uint64_t table_b = o->level == KC_SPEED_BEST ? 0 : o->level == KC_SPEED_BETTER ? kc_zbetter_table_bytes() : (o->level == KC_SPEED_DEFAULT ? kc_zdfast_table_bytes() : kc_zfast_table_bytes());
-    const uint64_t per_block = 2 * (bsz / 4 + 8) * 8 + (bsz + 64) + sizeof(KcBlkMeta);
-    const uint64_t hist0 = (o->dict != nullptr) ? o->dict_len : 0;
-    const uint64_t blocks = (len + bsz - 1) / bsz + n_cuts;  // every Flush point can add a block, at the full per-block strides
-    const uint64_t enc = ((uint64_t)kc_zstd_max_encoded_size(o, (int64_t)len) + 3 * n_cuts + 3 + 15) & ~(uint64_t)15;
-    return table_b + blocks * per_block + enc + (hist0 ? hist0 + len : 0) + 64;
-}
-
 // Scratch a batch may ask for: the configured ceiling, or 85 % of what is free plus what this context already owns (re-used).
 uint64_t scratch_budget(kc_ctx* c) {
     uint64_t budget = c->max_scratch_bytes;
@@ -903,12 +765,8 @@ kc_status feed_finish(kc_ctx* c, bool* redo_needed) {
     HIPCHK(c, hipMemcpyAsync(errv, c->errflag.p, 64, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
-    if (errv[0] != 0) {
-        char b[96];
-        snprintf(b, sizeof(b), "device invariant violated (code %u)", errv[0]);
-        c->err = b;
-        return errv[0] == 100u ? KC_ERR_UNSUPPORTED : KC_ERR_INTERNAL;
-    }
+    const kc_status sv = device_verdict(c, errv);
+    if (sv != KC_OK) return sv;
     *redo_needed = false;
     for (uint32_t i = 0; i < n_units; i++) if (redo[i]) *redo_needed = true;
     return KC_OK;
@@ -933,18 +791,13 @@ kc_status kc_zstd_encode_units_dev(kc_ctx* c, const kc_zstd_opts* o, const uint8
     kc_status s = check_supported(c, o);
     if (s != KC_OK) return s;
     HIPCHK(c, hipSetDevice(c->device));
-    for (uint32_t i = 0; i < n_units; i++) {
-        if (unit_off[i + 1] < unit_off[i]) { c->err = "unit_off not ascending"; return KC_ERR_BAD_ARG; }
-        if (unit_off[i + 1] - unit_off[i] > KC_MAX_UNIT_BYTES) {
-            c->err = "unit larger than 1 GiB: not served by the device path";
-            return KC_ERR_UNSUPPORTED;
-        }
-    }
+    if ((s = validate_units(c, o, unit_off, n_units)) != KC_OK) return s;
     out_off[0] = 0;
     c->last_batches = 0;
     uint64_t pos = 0;
     uint32_t i0 = 0;
     std::vector<uint64_t> tmp;
+    auto unit_len = [&](uint32_t i) { return unit_off[i + 1] - unit_off[i]; };
     auto unit_scratch = [&](uint32_t i) {
         const uint64_t nc = c->cuts ? c->cut_off[i + 1] - c->cut_off[i] : 0;
         return zstd_unit_scratch(o, unit_off[i + 1] - unit_off[i], nc);
@@ -953,17 +806,7 @@ kc_status kc_zstd_encode_units_dev(kc_ctx* c, const kc_zstd_opts* o, const uint8
     for (int attempt = 0;; attempt++) {
         bool oom = false;
         while (i0 < n_units) {
-            uint32_t i1 = i0;
-            const uint64_t cap_bytes = o->level == KC_SPEED_BETTER ? ((uint64_t)1 << 30) : c->max_batch_bytes;  // better: 4 MiB of tables per unit
-            const uint32_t cap_units = o->level == KC_SPEED_BETTER ? 16384u : 0xFFFFFFFFu;
-            uint64_t scratch = 0;
-            while (i1 < n_units) {
-                const uint64_t us = unit_scratch(i1);
-                // ensure() over-allocates by 1/8
-                if (i1 > i0 && (unit_off[i1 + 1] - unit_off[i0] > cap_bytes || i1 - i0 >= cap_units || (scratch + us) + ((scratch + us) >> 3) > budget)) break;
-                scratch += us;
-                i1++;
-            }
+            const uint32_t i1 = zenc_cut_batch(i0, n_units, unit_len, unit_scratch, zenc_level_caps(o, c->max_batch_bytes), budget);
             const uint32_t nb = i1 - i0;
             tmp.resize(nb + 1);
             uint64_t produced = 0;
@@ -1009,8 +852,8 @@ kc_status kc_zstd_encode_units_dev_begin(kc_ctx* c, const kc_zstd_opts* o, const
     if (s != KC_OK) return s;
     HIPCHK(c, hipSetDevice(c->device));
     if ((s = validate_units(c, o, unit_off, n_units)) != KC_OK) return s;
-    const uint64_t cap_bytes = o->level == KC_SPEED_BETTER ? ((uint64_t)1 << 30) : c->max_batch_bytes;
-    if (unit_off[n_units] - unit_off[0] > cap_bytes || (o->level == KC_SPEED_BETTER && n_units > 16384u)) {
+    const KcZencCaps caps = zenc_level_caps(o, c->max_batch_bytes);
+    if (unit_off[n_units] - unit_off[0] > caps.bytes || n_units > caps.units) {
         c->err = "begin/end serves one device batch; use kc_zstd_encode_units_dev for larger inputs";
         return KC_ERR_UNSUPPORTED;
     }

@@ -1,12 +1,15 @@
 #pragma once
 // kc_host.h — internal header of the host side of the C ABI (include/kcgpu.h): the context, its scratch buffers and the batch
-// records shared by the translation units kc_ctx.cpp (options, context), kc_batch.cpp (the zstd device pipeline), kc_zstd_host.cpp
+// records shared by the translation units kc_ctx.cpp (context), kc_batch.cpp (the zstd device pipeline), kc_zstd_host.cpp
 // (host-buffer entry points), kc_jobs.cpp (WithConcurrentBlocks), kc_s2_api.cpp (S2), kc_hook.cpp (the WriterCustomEncoder hook) and the
 // decoders' entry points: kc_zstd_dec_api.cpp (DecodeAll), kc_s2_dec_api.cpp (s2.Reader / s2.Decode), kc_s2_ranges_api.cpp (ReadAt),
 // kc_flate_api.cpp (flate / gzip readers), kc_zstd_dstream_api.cpp and kc_s2_rstream_api.cpp (the stream readers).  The decoders'
 // host sequences themselves are not here: they live in headers over a small device interface (kc_decdev_host.h; kc_zdec_host.h,
 // kc_s2dec_host.h, kc_s2ranges_host.h, kc_flate_host.h, kc_zdstream_host.h, kc_s2rstream_host.h) that know neither HIP nor the
 // context, and the entry points hand them HipDevice (kc_decdev_hip.h).
+// The zstd encoder's host rules are not here either: the batch plan, the staging slot and scratch of a unit, the parameter fill, the path
+// predicates, the re-run rule and the batch cutter live in kc_zenc_host.h (no HIP call, no context), which kc_batch.cpp runs on the
+// device and the wave emulator runs over plain memory; the option functions are kc_zstd_opts.cpp (include/kcgpu.h alone).
 // Not installed: the boundary is include/kcgpu.h.
 // There is deliberately NO CPU fallback in this library: when the device path cannot serve a
 // request it returns KC_ERR_UNSUPPORTED / KC_ERR_NO_DEVICE and the caller (the Go shim)
@@ -30,13 +33,10 @@
 #include "../../include/kcgpu.h"
 #include "kc_kernels.h"
 #include "kc_zdec_host.h"
+#include "kc_zenc_host.h"
 
 
 namespace kci {
-
-const int kMinWindowSize = 1 << 10;          // zstd/decoder_options.go MinWindowSize
-const int kMaxWindowSize = 1 << 29;          // zstd MaxWindowSize
-const int kMaxCompressedBlockSize = 128 << 10;  // zstd/blockdec.go:40
 
 struct DevBuf {
     void* p = nullptr;
@@ -79,17 +79,11 @@ struct ChunkFeed {
     uint64_t* loc_off = nullptr;
 };
 
-// Host-side layout of one device batch.  Lives in the context: the H2D copies of its arrays are asynchronous, so the arrays must
-// outlive batch_begin (they are overwritten by the next batch of the same context, after batch_end synchronised the stream).
-struct Plan {
-    uint32_t n_units = 0, n_blocks = 0;
-    std::vector<uint32_t> blk0;       // n+1
-    std::vector<uint64_t> stage_off;  // n+1
-    std::vector<uint32_t> blk_start, unit_flags;  // streams with Flush points: per block / per unit (see KcMatchParams)
+// Host-side layout of one device batch (zstd: KcZencPlan, kc_zenc_host.h).  Lives in the context: the H2D copies of its arrays are
+// asynchronous, so the arrays must outlive batch_begin (they are overwritten by the next batch of the same context, after batch_end
+// synchronised the stream).
+struct Plan : KcZencPlan {
     std::vector<uint64_t> stage64;    // S2: n+1 staging slot offsets (64-byte aligned)
-    std::vector<uint64_t> rel_off;    // n+1 unit offsets relative to the batch base
-    uint32_t seq_stride = 0, lit_stride = 0;
-    uint64_t max_unit_bytes = 0;      // longest unit of the batch
 };
 
 }  // namespace kci
@@ -280,13 +274,11 @@ using namespace kci;
 namespace kci {
 // kc_batch.cpp: the zstd device pipeline
 kc_status check_supported(kc_ctx* c, const kc_zstd_opts* o);
-size_t match_table_bytes(int level);
+inline size_t match_table_bytes(int level) { return (size_t)zenc_table_bytes(level); }
 kc_status launch_match(kc_ctx* c, const KcMatchParams& mp, const uint64_t* unit_off, uint32_t n_units, uint32_t n_launch, int bs, hipStream_t st, int level);
-uint32_t plan_stream_blocks(uint64_t bs, uint64_t len, const uint64_t* cuts, uint64_t n_cuts, std::vector<uint32_t>* starts, uint32_t* flags);
 kc_status batch_begin(kc_ctx* c, const kc_zstd_opts* o, const uint8_t* d_src_base, const uint64_t* unit_off, uint32_t n_units,
                       uint8_t* d_dst, uint64_t dst_cap, ChunkFeed* feed = nullptr);
 kc_status batch_end(kc_ctx* c, uint64_t* out_off_host, uint64_t* produced);
-uint64_t zstd_unit_scratch(const kc_zstd_opts* o, uint64_t len, uint64_t n_cuts = 0);
 uint64_t scratch_budget(kc_ctx* c);
 kc_status feed_finish(kc_ctx* c, bool* redo_needed);
 kc_status run_batch(kc_ctx* c, const kc_zstd_opts* o, const uint8_t* d_src_base, const uint64_t* unit_off, uint32_t n_units,

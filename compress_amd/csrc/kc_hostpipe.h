@@ -397,7 +397,7 @@ inline kc_status host_overlapped_zstd(kc_ctx* c, const kc_zstd_opts* o, const ui
     if (o->dict != nullptr || o->level == KC_SPEED_BETTER || total > c->max_batch_bytes) { c->err.clear(); return KC_ERR_UNSUPPORTED; }
     uint64_t need = 0, scratch = 0;
     for (uint32_t i = 0; i < n_units; i++) {
-        need += ((uint64_t)kc_zstd_max_encoded_size(o, (int64_t)(unit_off[i + 1] - unit_off[i])) + 15) & ~(uint64_t)15;
+        need += zenc_unit_slot(o, unit_off[i + 1] - unit_off[i], false, 0);
         scratch += zstd_unit_scratch(o, unit_off[i + 1] - unit_off[i]);
     }
     if (scratch + (scratch >> 3) + total + need > scratch_budget(c)) { c->err.clear(); return KC_ERR_UNSUPPORTED; }  // many small units: several batches

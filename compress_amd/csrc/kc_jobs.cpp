@@ -163,20 +163,17 @@ kc_status kc_zstd_encode_jobs(kc_ctx* c, const kc_zstd_opts* o, const uint8_t* s
     std::vector<uint64_t> boff, oo;
     uint32_t k0 = 0;
     for (int attempt = 0; k0 < nj;) {
-        uint32_t k1 = k0;
-        uint64_t scratch = 0, bytes = 0, need = 0, maxUnit = 16;
-        while (k1 < nj) {
-            const uint64_t us = zstd_unit_scratch(o, jlen[k1]);
-            if (k1 > k0 && (bytes + jlen[k1] > c->max_batch_bytes || (scratch + us) + ((scratch + us) >> 3) > budget)) break;
-            scratch += us;
-            bytes += jlen[k1];
-            need += ((uint64_t)kc_zstd_max_encoded_size(o, (int64_t)jlen[k1]) + 15) & ~(uint64_t)15;
-            maxUnit = std::max(maxUnit, jlen[k1]);
-            k1++;
-        }
+        const uint32_t k1 = zenc_cut_batch(k0, nj, [&](uint32_t k) { return jlen[k]; }, [&](uint32_t k) { return zstd_unit_scratch(o, jlen[k]); },
+                                           KcZencCaps{c->max_batch_bytes, 0xFFFFFFFFu}, budget);  // (the budget alone bounds the units, at every level)
         const uint32_t nb = k1 - k0;
-        int pos_bits = 1;
-        while (((uint64_t)1 << pos_bits) <= maxUnit + 2) pos_bits++;  // batch_begin's, for this batch
+        boff.assign(nb + 1, 0);
+        uint64_t need = 0;
+        for (uint32_t k = 0; k < nb; k++) {
+            boff[k + 1] = boff[k] + jlen[k0 + k];
+            need += zenc_unit_slot(o, jlen[k0 + k], false, 0);
+        }
+        const uint64_t bytes = boff[nb];
+        const int pos_bits = zenc_pos_bits(0, zenc_max_unit(boff.data(), nb));  // the plan's, for this batch
         const bool primeHost = tb != 0 && c->cfg.job_prime == 0;  // (default: kc_zstd_prime_kernel, from the prefix bytes staged below)
         if (primeHost) {
             try { tabs.assign((size_t)nb * tb, 0); } catch (...) { c->err = "host memory for the jobs' tables"; return KC_ERR_UNSUPPORTED; }
@@ -191,9 +188,7 @@ kc_status kc_zstd_encode_jobs(kc_ctx* c, const kc_zstd_opts* o, const uint8_t* s
             for (auto& x : th) x.join();
         }
         if ((s = ensure(c, c->tmp_src, bytes + 64)) || (s = ensure(c, c->tmp_dst, need + 64))) return s;
-        boff.assign(nb + 1, 0);
         for (uint32_t k = 0; k < nb; k++) {
-            boff[k + 1] = boff[k] + jlen[k0 + k];
             if (jlen[k0 + k]) HIPCHK(c, hipMemcpyAsync((uint8_t*)c->tmp_src.p + boff[k], src + lo[k0 + k] - jhist[k0 + k], jlen[k0 + k], hipMemcpyHostToDevice, c->stream));
         }
         oo.assign(nb + 1, 0);

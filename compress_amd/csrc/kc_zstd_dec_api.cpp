@@ -29,7 +29,7 @@ int kc_zstd_dopts_max_memory(kc_zstd_dopts* o, uint64_t n) {  // WithDecoderMaxM
     return 0;
 }
 int kc_zstd_dopts_max_window(kc_zstd_dopts* o, uint64_t n) {  // WithDecoderMaxWindow, zstd/decoder_options.go:150-161
-    if (!o || n < (uint64_t)kMinWindowSize || n > ((uint64_t)1 << 41) + 7 * ((uint64_t)1 << 38)) return -1;
+    if (!o || n < (uint64_t)KC_ZSTD_MIN_WINDOW_SIZE || n > ((uint64_t)1 << 41) + 7 * ((uint64_t)1 << 38)) return -1;
     o->max_window = n;
     return 0;
 }

@@ -46,7 +46,7 @@ kc_status kc_zstd_encode_units(kc_ctx* c, const kc_zstd_opts* o, const uint8_t* 
     }
     uint64_t need = 0;
     for (uint32_t i = 0; i < n_units; i++)
-        need += ((uint64_t)kc_zstd_max_encoded_size(o, (int64_t)(unit_off[i + 1] - unit_off[i])) + (c->cuts ? 3 * (c->cut_off[i + 1] - c->cut_off[i]) + 3 : 0) + 15) & ~(uint64_t)15;
+        need += zenc_unit_slot(o, unit_off[i + 1] - unit_off[i], c->cuts != nullptr, c->cuts ? c->cut_off[i + 1] - c->cut_off[i] : 0);
     if ((s = ensure(c, c->tmp_src, total + 64)) || (s = ensure(c, c->tmp_dst, need + 64))) return s;
     HIPCHK(c, hipMemcpyAsync(c->tmp_src.p, src + unit_off[0], total, hipMemcpyHostToDevice, c->stream));
     std::vector<uint64_t> rel(n_units + 1);
@@ -188,45 +188,35 @@ kc_status kc_zstd_debug_parse_dev(kc_ctx* c, const kc_zstd_opts* o, const uint8_
     if (s != KC_OK) return s;
     HIPCHK(c, hipSetDevice(c->device));
     const int bs = o->block_size;
-    std::vector<uint32_t> blk0(n_units + 1);
-    uint32_t nb = 0;
-    for (uint32_t i = 0; i < n_units; i++) { blk0[i] = nb; nb += (uint32_t)((unit_off[i + 1] - unit_off[i] + bs - 1) / bs); }
-    blk0[n_units] = nb;
+    // the batch's plan without its dictionary (refused below, where it always was) and repeat offsets: the parse alone, from {1, 4, 8}
+    kc_zstd_opts od = *o;
+    od.dict = nullptr;
+    od.dict_len = 0;
+    od.dict_offsets[0] = 1; od.dict_offsets[1] = 4; od.dict_offsets[2] = 8;
+    Plan& pl = c->plan;
+    zenc_plan(&od, unit_off, n_units, nullptr, KcZencCuts(), pl);
+    const uint32_t nb = pl.n_blocks, seq_stride = pl.seq_stride;
     if (nb > blk_cap) return KC_ERR_DST_TOO_SMALL;
-    const uint32_t seq_stride = (uint32_t)(bs / 4 + 8);
+    const KcZencReserve r = zenc_reserve(&od, pl);
     if ((s = ensure(c, c->unit_off, (n_units + 1) * 8)) || (s = ensure(c, c->unit_blk0, (n_units + 1) * 4)) ||
-        (s = ensure(c, c->seqs, (size_t)nb * seq_stride * 8)) || (s = ensure(c, c->meta, (size_t)nb * sizeof(KcBlkMeta))))
+        (s = ensure(c, c->seqs, r.seqs)) || (s = ensure(c, c->meta, r.meta)))
         return s;
     HIPCHK(c, hipMemcpyAsync(c->unit_off.p, unit_off, (n_units + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->unit_blk0.p, blk0.data(), (n_units + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->unit_blk0.p, pl.blk0.data(), (n_units + 1) * 4, hipMemcpyHostToDevice, c->stream));
     c->up_ptr[0] = c->up_ptr[1] = c->up_ptr[2] = nullptr;  // (the zstd batch path re-uploads its layout arrays)
+    KcZencBufs b;
+    b.src = d_src + unit_off[0];  // (src_end = d_src + unit_off[n_units]; the offsets on the device are the caller's)
+    b.unit_off = (const uint64_t*)c->unit_off.p;
+    b.unit_blk0 = (const uint32_t*)c->unit_blk0.p;
+    b.seqs = (uint64_t*)c->seqs.p;
+    b.meta = (KcBlkMeta*)c->meta.p;
+    KcZencSteer cx;  // (no stream mode; its own defaults and clamp of the speculation policy)
+    cx.spec_w0 = c->cfg.spec_w0 >= 0 ? std::min<int64_t>(c->cfg.spec_w0, 8) : 1;
+    cx.spec_grow = c->cfg.spec_grow >= 0 ? c->cfg.spec_grow : 2;
     KcMatchParams mp;
-    memset(&mp, 0, sizeof(mp));
+    KcEntropyParams ep;
+    zenc_fill_params(&od, pl, b, cx, mp, ep);
     mp.src = d_src;
-    mp.src_end = d_src + unit_off[n_units];
-    mp.unit_off = (const uint64_t*)c->unit_off.p;
-    mp.unit_blk0 = (const uint32_t*)c->unit_blk0.p;
-    mp.seqs = (uint64_t*)c->seqs.p;
-    mp.meta = (KcBlkMeta*)c->meta.p;
-    mp.seq_stride = seq_stride;
-    mp.block_size = bs;
-    mp.max_match_off = o->window_size;
-    mp.spec_w0 = c->cfg.spec_w0 >= 0 ? (int)c->cfg.spec_w0 : 1;
-    mp.spec_grow = c->cfg.spec_grow >= 0 ? (int)c->cfg.spec_grow : 2;
-    if (mp.spec_w0 < 1) mp.spec_w0 = 1;
-    if (mp.spec_w0 > 8) mp.spec_w0 = 8;
-    mp.hist0 = 0;
-    mp.rep1 = 1;
-    mp.rep2 = 4;
-    mp.rep3 = 8;
-    {
-        uint64_t maxLen = 16;
-        for (uint32_t i = 0; i < n_units; i++) maxLen = std::max<uint64_t>(maxLen, unit_off[i + 1] - unit_off[i]);
-        c->plan.max_unit_bytes = maxLen;
-        int pb = 1;
-        while (((uint64_t)1 << pb) <= maxLen + 2) pb++;
-        mp.pos_bits = pb;
-    }
     if (o->dict != nullptr && o->dict_len > 0) { c->err = "debug parse does not take dictionaries"; return KC_ERR_UNSUPPORTED; }
     if ((s = launch_match(c, mp, unit_off, n_units, n_units, bs, c->stream, o->level)) != KC_OK) return s;
     std::vector<KcBlkMeta> meta(nb);

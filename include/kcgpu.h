@@ -84,6 +84,11 @@ typedef struct {
                                    * first block; otherwise the first block starts from it (kc_zstd_encode_streams*) */
 } kc_zstd_opts;
 
+/* the limits the option functions and the device path check */
+#define KC_ZSTD_MIN_WINDOW_SIZE (1 << 10)      /* zstd/decoder_options.go MinWindowSize */
+#define KC_ZSTD_MAX_WINDOW_SIZE (1 << 29)      /* zstd MaxWindowSize */
+#define KC_ZSTD_MAX_BLOCK_SIZE (128 << 10)     /* maxCompressedBlockSize, zstd/blockdec.go:40 */
+
 /* encoderOptions.setDefault, zstd/encoder_options.go:36-48 */
 void kc_zstd_opts_default(kc_zstd_opts* o);
 /* WithEncoderLevel, zstd/encoder_options.go:236-266 */

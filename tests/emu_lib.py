@@ -21,7 +21,7 @@ _L = None
 
 def build(force=False):
     srcs = [os.path.join(EMU, "kcemu.cpp"), os.path.join(EMU, "hipemu.cpp")]
-    deps = srcs + [os.path.join(EMU, "hip", "hip_runtime.h")] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))]
+    deps = srcs + [os.path.join(EMU, "hip", "hip_runtime.h")] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip", ".cpp"))]
     if not force and os.path.exists(OUT) and all(os.path.getmtime(d) <= os.path.getmtime(OUT) for d in deps):
         return OUT
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
@@ -217,13 +217,10 @@ def zfast_parse(units, block_size=65536, window=4 << 20, spec_w0=8, stream_mode=
     o = (-al.ctypes.data) % 16
     al[o:o + len(src)] = src
     base = al.ctypes.data + o
-    stride = block_size // 4 + 8
+    stride = lib().kcemu_zenc_seq_stride(block_size)
     seqs = np.zeros(max(nb, 1) * stride, dtype=np.uint64)
     meta = np.zeros(max(nb, 1) * 8, dtype=np.uint32)
-    maxlen = max([len(u) for u in units] + [16])
-    pb = 1
-    while (1 << pb) <= maxlen + 2:
-        pb += 1
+    pb = lib().kcemu_zenc_pos_bits(C.c_uint64(0), C.c_uint64(max([len(u) for u in units] + [0])))
     r = lib().kcemu_zfast_parse(base, off.ctypes.data, n, block_size, window, 0, 1, 4, stream_mode, None, seqs.ctypes.data, meta.ctypes.data, stride,
                                 blk0.ctypes.data, spec_w0, pb)
     assert r == 0
@@ -256,13 +253,10 @@ def zfast_parse_grp(units, block_size=65536, window=4 << 20, spec_w0=1, spec_gro
     o = (-al.ctypes.data) % 16
     al[o:o + len(src)] = src
     base = al.ctypes.data + o
-    stride = block_size // 4 + 8
+    stride = lib().kcemu_zenc_seq_stride(block_size)
     seqs = np.zeros(max(nb, 1) * stride, dtype=np.uint64)
     meta = np.zeros(max(nb, 1) * 8, dtype=np.uint32)
-    maxlen = max([len(u) for u in units] + [16])
-    pb = 1
-    while (1 << pb) <= maxlen + 2:
-        pb += 1
+    pb = lib().kcemu_zenc_pos_bits(C.c_uint64(0), C.c_uint64(max([len(u) for u in units] + [0])))
     if slots is not None:
         pb = slots
     nslot = (n + 7) // 8 * 8
@@ -309,7 +303,7 @@ def zbest_parse(units, block_size=131072, window=8 << 20, stream_mode=0, n_slots
     o = (-al.ctypes.data) % 16
     al[o:o + len(src)] = src
     base = al.ctypes.data + o
-    stride = block_size // 4 + 8
+    stride = lib().kcemu_zenc_seq_stride(block_size)
     seqs = np.zeros(max(nb, 1) * stride, dtype=np.uint64)
     meta = np.zeros(max(nb, 1) * 8, dtype=np.uint32)
     st = _zbest_state
@@ -415,40 +409,47 @@ def xxh_fin(units, raw_flags, block_size, out_positions, mode, frame_header=9):
     return dst, stage, soff, sizes, xxh
 
 
-@_fanned(serial_if=lambda kw: kw.get("fused") is not None)  # (batch_end's sequence is one batch: its counters and the contiguous output)
+@_fanned(serial_if=lambda kw: kw.get("fused") is not None or kw.get("flush_at") is not None)  # (batch_end's sequence is one batch: its counters and the contiguous output; Flush points go by unit index)
 def zstd_frames(units, block_size=None, window=None, crc=True, single=-1, full_zero=True, stream_mode=0, use_grp=False, tuned=0,
-                max_encoded_size=None, level=1, no_entropy=False, all_lit_entropy=False, fused=None):
-    """The device's whole SpeedFastest EncodeAll pipeline on the emulator (checksum, match finder, entropy stage): one frame per unit.
-    Returns (list of frames, error flag, re-run flag)."""
-    if level != 1:
-        use_grp = level  # (selects the level's match finder in kcemu_zstd_frames)
-    if window is None:
-        window = (4 << 20) if level == 1 else (8 << 20)  # encoder_options.go:254-266
-    if block_size is None:
-        block_size = min(65536 if level == 1 else 131072, window)
+                max_encoded_size=None, level=1, no_entropy=False, all_lit_entropy=False, fused=None, flush_at=None):
+    """The device's zstd encode batch on the emulator (checksum, match finder, entropy stage, speculation re-run) under the library's
+    own host rules (kcemu_zstd_batch: the plan, the parameter fill and the per-level defaults are kc_zenc_host.h's): one frame per
+    unit.  flush_at: per unit the Flush positions of its stream (kc_zstd_encode_streams_cuts).  max_encoded_size: the caller's bound of
+    one unit's frame; the staging slots are the library's and may not be larger than it gives.  Returns (list of frames, error flag, units the re-run took)."""
     n = len(units)
     off = np.zeros(n + 1, dtype=np.uint64)
-    soff = np.zeros(n + 1, dtype=np.uint64)
     for i, u in enumerate(units):
         off[i + 1] = off[i] + len(u)
-        mes = max_encoded_size(len(u)) if max_encoded_size else len(u) + 64 + 3 * (len(u) // block_size + 2)
-        soff[i + 1] = soff[i] + ((mes + 15) & ~15)
     src = np.frombuffer(b"".join(units) + b"\0" * 64, dtype=np.uint8).copy()
     al = np.zeros(len(src) + 32, dtype=np.uint8)
     o = (-al.ctypes.data) % 16
     al[o:o + len(src)] = src
-    stage = np.zeros(int(soff[n]) + 64, dtype=np.uint8)
+    cut_off = cuts = None
+    if flush_at is not None:
+        assert len(flush_at) == n
+        cut_off = np.cumsum([0] + [len(c) for c in flush_at]).astype(np.uint64)
+        cuts = np.ascontiguousarray([x for c in flush_at for x in sorted(c)] + [0], dtype=np.uint64)
+    soff = np.zeros(n + 1, dtype=np.uint64)
     sizes = np.zeros(n + 1, dtype=np.uint32)
     err = np.zeros(4, dtype=np.uint32)
-    dst = np.full(int(soff[n]) + 64, 0xAA, dtype=np.uint8) if fused is not None else None
     doff = np.zeros(n + 2, dtype=np.uint64)
     L = lib()
-    L.kcemu_zstd_frames.restype = C.c_int
-    L.kcemu_zstd_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_int] * 9 + [C.c_void_p] * 6 + [C.c_int]
-    r = L.kcemu_zstd_frames(al.ctypes.data + o, off.ctypes.data, n, block_size, window, int(crc), single, int(full_zero), stream_mode, int(use_grp), tuned,
-                            int(no_entropy) | (int(all_lit_entropy) << 1), stage.ctypes.data, soff.ctypes.data, sizes.ctypes.data, err.ctypes.data,
-                            dst.ctypes.data if dst is not None else None, doff.ctypes.data, int(fused or 0))
-    assert r == 0
+    L.kcemu_zstd_batch.restype = C.c_int
+    L.kcemu_zstd_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_int] * 10 + [C.c_void_p] * 3 + [C.c_uint64] + [C.c_void_p] * 5 + [C.c_int]
+
+    def call(stage, dst):
+        return L.kcemu_zstd_batch(al.ctypes.data + o, off.ctypes.data, n, level, block_size or 0, window or 0, int(crc), single, int(full_zero), stream_mode,
+                                   int(bool(use_grp)), tuned, int(no_entropy) | (int(all_lit_entropy) << 1),
+                                   None if cut_off is None else cut_off.ctypes.data, None if cuts is None else cuts.ctypes.data,
+                                   None if stage is None else stage.ctypes.data, 0 if stage is None else len(stage) - 64, soff.ctypes.data, sizes.ctypes.data,
+                                   err.ctypes.data, None if dst is None else dst.ctypes.data, doff.ctypes.data, int(fused or 0))
+    assert call(None, None) == 0  # the plan alone: the staging slots
+    if max_encoded_size is not None and flush_at is None:
+        assert all(int(soff[i + 1] - soff[i]) <= (max_encoded_size(len(u)) + 15) & ~15 for i, u in enumerate(units))
+    stage = np.zeros(int(soff[n]) + 64, dtype=np.uint8)
+    dst = np.full(int(soff[n]) + 64, 0xAA, dtype=np.uint8) if fused is not None else None
+    r = call(stage, dst)
+    assert r == 0, r
     if fused is not None:  # batch_end's sequence: size scan, checksum (+ raw payloads), compaction -> the contiguous output
         assert int(doff[n]) == int(sizes[:n].sum()) and np.all(dst[int(doff[n]):] == 0xAA)
         if tuned & 0x100:  # (with the pre-scan: how many units it settled)

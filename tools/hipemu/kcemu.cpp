@@ -31,6 +31,8 @@
 #include "../../compress_amd/csrc/kc_s2dec_host.h"
 #include "../../compress_amd/csrc/kc_s2ranges_host.h"
 #include "../../compress_amd/csrc/kc_flate_host.h"
+#include "../../compress_amd/csrc/kc_zstd_opts.cpp"  // (host code: the encoder's option functions)
+#include "../../compress_amd/csrc/kc_zenc_host.h"    // (host code: the rules of the zstd encode batch)
 
 // The decoders' device (kc_decdev_host.h) over plain memory: every buffer a heap block of exactly the size asked for (a write outside
 // it is one outside a heap block), filled with 0xA7 when it is made; copies are memcpy; the kernels run on the emulator.
@@ -369,130 +371,182 @@ int kcemu_xxh_fin(const uint8_t* src, const uint64_t* unit_off, uint32_t n, uint
     return 0;
 }
 
-// The whole SpeedFastest EncodeAll pipeline of the device on the emulator: checksum kernel, match finder (LDS-table kernel, or with
-// use_grp = 1 the HBM-table group kernel in the form `tuned`; use_grp = 2 / 3 / 4: the SpeedDefault / SpeedBetterCompression /
-// SpeedBestCompression match finders), entropy stage — the frames as they sit in the staging slots (raw blocks'
-// payloads included: no rawdef), with the host's layout rules (seq_stride, lit_stride: kc_batch.cpp batch_begin).
-int kcemu_zstd_frames(const uint8_t* src, const uint64_t* unit_off, uint32_t n, int block_size, int window, int crc, int single, int full_zero,
-                      int stream_mode, int use_grp, int tuned, int entropy_opts /* bit 0: no_entropy, bit 1: all_lit_entropy */, uint8_t* stage, const uint64_t* stage_off, uint32_t* out_size, uint32_t* err_out,
-                      uint8_t* fused_dst /* or null */, uint64_t* fused_off, int fused_mode) {
-    std::vector<uint32_t> blk0(n + 1, 0);
-    for (uint32_t i = 0; i < n; i++) {
-        const uint64_t len = unit_off[i + 1] - unit_off[i];
-        blk0[i + 1] = blk0[i] + (uint32_t)((len + (uint64_t)block_size - 1) / (uint64_t)block_size);
-    }
-    const uint32_t nb = blk0[n];
-    const uint32_t seq_stride = (uint32_t)(block_size / 4 + 8), lit_stride = (uint32_t)(block_size + 64);
-    std::vector<uint64_t> seqs((size_t)(nb + 1) * seq_stride, 0), aux((size_t)(nb + 1) * seq_stride, 0), xxh(n + 1, 0);
-    std::vector<uint8_t> lits((size_t)(nb + 1) * lit_stride, 0), redo_blk(nb + 1, 0), predef(kc_fse_predef_bytes() + 64, 0);
+// the encode batch's stride and position width (kc_zenc_host.h) for the tests that call single kernels with buffers of their own
+uint32_t kcemu_zenc_seq_stride(int block_size) { return kci::zenc_seq_stride(block_size); }
+int kcemu_zenc_pos_bits(uint64_t hist0, uint64_t max_unit) { return kci::zenc_pos_bits(hist0, std::max<uint64_t>(max_unit, 16)); }
+
+// The options of a kcemu_zstd_batch call, resolved by the library's own option functions (block_size / window 0: the level's)
+static void kcemu_zstd_opts(kc_zstd_opts& o, int level, int block_size, int window, int crc, int single, int full_zero, int entropy_opts) {
+    kc_zstd_opts_default(&o);
+    kc_zstd_opts_level(&o, level);
+    if (window > 0) kc_zstd_opts_window(&o, window);
+    if (block_size > 0 && block_size != o.block_size) { o.block_size = block_size; o.custom_block = 1; }  // (tests: block sizes no option function gives)
+    kc_zstd_opts_crc(&o, crc);
+    kc_zstd_opts_zero_frames(&o, full_zero);
+    kc_zstd_opts_no_entropy(&o, entropy_opts & 1);
+    if (entropy_opts & 2) kc_zstd_opts_all_lit_entropy(&o, 1);
+    if (single >= 0) kc_zstd_opts_single_segment(&o, single);
+}
+
+// The device's zstd encode batch on the emulator: the plan, the parameter fill, the path predicates and the speculation re-run are
+// the library's (kc_zenc_host.h, the rules kc_batch.cpp runs); the buffers are plain vectors and the kernels run on the emulator.
+// This function's own: the forced kernel forms — level 1: the LDS-table kernel (spec_w0 16), or with use_grp the HBM-table group
+// kernel in the form `tuned` (bit 8: the pre-scan asked for, as KC_OPT_ZFAST_PRESCAN 1 asks); levels 2 / 3 / 4: the level's match
+// finder, tables cleared per launch — the KC_EMU_SPEC_* overrides, and the view of the frames: with fused_dst null as they sit in
+// their staging slots (raw blocks' payloads included: no rawdef), else the contiguous output behind batch_end's finishing pass.
+// cut_off / cuts: null, or the streams' Flush points as kc_zstd_encode_streams_cuts takes them.  stage null: the plan alone
+// (stage_off: n + 1 slot offsets).  err_out: [0] device error flag, [1] units the re-run took, [2] raw-only frames, [3] units the
+// pre-scan settled.  Returns 0, -2 when stage_cap is below the plan's need, -3 when the re-run does not converge.
+int kcemu_zstd_batch(const uint8_t* src, const uint64_t* unit_off, uint32_t n, int level, int block_size, int window, int crc, int single, int full_zero,
+                     int stream_mode, int use_grp, int tuned, int entropy_opts /* bit 0: no_entropy, bit 1: all_lit_entropy */, const uint64_t* cut_off,
+                     const uint64_t* cuts, uint8_t* stage, uint64_t stage_cap, uint64_t* stage_off, uint32_t* out_size, uint32_t* err_out,
+                     uint8_t* fused_dst /* or null */, uint64_t* fused_off, int fused_mode) {
+    using namespace kci;
+    kc_zstd_opts o;
+    kcemu_zstd_opts(o, level, block_size, window, crc, single, full_zero, entropy_opts);
+    static const uint64_t none = 0;
+    KcZencCuts fl;
+    if (cut_off) { fl.cut_off = cut_off; fl.cuts = cuts ? cuts : &none; }
+    KcZencPlan pl;
+    zenc_plan(&o, unit_off, n, nullptr, fl, pl);
+    memcpy(stage_off, pl.stage_off.data(), (size_t)(n + 1) * 8);
+    if (!stage) return 0;
+    if (pl.need > stage_cap || !zenc_offsets_fit(&o, pl)) return -2;
+    const uint32_t nb = pl.n_blocks;
+    const KcZencReserve r = zenc_reserve(&o, pl);
+    std::vector<uint64_t> seqs(r.seqs / 8 + pl.seq_stride, 0), aux(r.aux / 8 + pl.seq_stride, 0), xxh(n + 1, 0);
+    std::vector<uint8_t> lits(r.lits + pl.lit_stride, 0), redo_blk(nb + 1, 0), pop_blk, predef(kc_fse_predef_bytes() + 64, 0);
     std::vector<KcBlkMeta> meta(nb + 1);
-    std::vector<uint32_t> redo(n + 1, 0), tables;
+    std::vector<KcRawDef> rawdef(nb + 1, KcRawDef{0, 0, 0, 0});
+    std::vector<uint32_t> redo(n + 1, 0), unit_raw(n + 1, 0), unit_done, probe_rel, list, tables;
+    std::vector<uint32_t> blk_start(pl.blk_start), unit_flags(pl.unit_flags);
+    blk_start.push_back(0);
+    unit_flags.push_back(0);
     uint32_t err[16] = {0};
-    uint64_t maxlen = 16;
-    for (uint32_t i = 0; i < n; i++) maxlen = std::max<uint64_t>(maxlen, unit_off[i + 1] - unit_off[i]);
-    int pb = 1;
-    while (((uint64_t)1 << pb) <= maxlen + 2) pb++;
+    const bool fuse_xxh = zenc_fuse_xxh(&o, pl, fused_dst != nullptr, false, false);
+    KcZencBufs b;
+    b.src = src + unit_off[0]; b.unit_off = pl.rel_off.data(); b.unit_blk0 = pl.blk0.data(); b.blk_start = blk_start.data(); b.unit_flags = unit_flags.data();
+    b.seqs = seqs.data(); b.aux = aux.data(); b.meta = meta.data(); b.lits = lits.data(); b.stage = stage; b.redo_blk = redo_blk.data();
+    b.stage_off = pl.stage_off.data(); b.xxh = xxh.data(); b.out_size = out_size; b.redo = redo.data(); b.errflag = err; b.unit_raw = unit_raw.data();
+    b.predef = predef.data(); b.rawdef = rawdef.data();
+    KcZencSteer cx;
+    cx.stream_mode = stream_mode;
+    cx.fuse_xxh = fuse_xxh;
+    if (level == KC_SPEED_DEFAULT) {  // (tests: other speculation policies = other round shapes)
+        if (const char* e = getenv("KC_EMU_SPEC_W0")) cx.spec_w0 = atoi(e);
+        if (const char* e = getenv("KC_EMU_SPEC_GROW")) cx.spec_grow = atoi(e);
+    }
     KcMatchParams M;
-    memset(&M, 0, sizeof(M));
-    M.src = src; M.src_end = src + unit_off[n]; M.unit_off = unit_off; M.unit_blk0 = blk0.data(); M.seqs = seqs.data(); M.meta = meta.data();
-    M.seq_stride = seq_stride; M.block_size = block_size; M.max_match_off = window; M.pos_bits = pb; M.rep1 = 1; M.rep2 = 4; M.rep3 = 8;
-    M.stream_mode = stream_mode;
+    KcEntropyParams E;
+    zenc_fill_params(&o, pl, b, cx, M, E);
+    if (fused_dst == nullptr) E.rawdef = nullptr;  // the frames are read in their slots
     kc_launch_fse_predef_init(predef.data(), nullptr);
-    if (crc) {
-        hipemu::set_group(4);
-        kc_launch_xxh64(src, unit_off, n, xxh.data(), nullptr);
-        hipemu::set_group(64);
-    }
-    // the no-match pre-scan in front of the match finder (tuned bit 8; kc_batch.cpp batch_begin runs it on fused batches only)
-    const bool prescan = (tuned & 0x100) != 0 && fused_dst != nullptr && crc && use_grp <= 1;
+    const bool prescan = zenc_run_prescan(&o, pl, (tuned & 0x100) ? 1 : 0, false, fuse_xxh, stream_mode);
     tuned &= 0xFF;
-    std::vector<KcRawDef> rawdef;
-    std::vector<uint32_t> unit_raw, unit_done, probe_rel;
-    if (fused_dst != nullptr) {
-        rawdef.assign(nb + 1, KcRawDef{0, 0, 0, 0});
-        unit_raw.assign(n + 1, 0);
-    }
     if (prescan) {
         probe_rel.resize(8192);
-        const uint32_t np = kc_zfast_probe_positions(block_size, probe_rel.data(), (uint32_t)probe_rel.size());
+        const uint32_t np = kc_zfast_probe_positions(o.block_size, probe_rel.data(), (uint32_t)probe_rel.size());
         unit_done.assign(n + 1, 0xFFFFFFFFu);
-        KcPrescanParams Q;
-        memset(&Q, 0, sizeof(Q));
-        Q.src = src; Q.unit_off = unit_off; Q.unit_blk0 = blk0.data(); Q.n_units = n; Q.block_size = block_size; Q.probe_rel = probe_rel.data();
-        Q.n_probe = np; Q.rep1 = 1; Q.rep2 = 4; Q.meta = meta.data(); Q.unit_done = unit_done.data(); Q.stage = stage; Q.stage_off = stage_off;
-        Q.out_size = out_size; Q.rawdef = rawdef.data(); Q.unit_raw = unit_raw.data(); Q.window_size = window; Q.crc = crc; Q.single = single;
+        const KcPrescanParams Q = zenc_prescan_params(&o, pl, M, E, probe_rel.data(), np, unit_done.data());
         kc_launch_zfast_prescan(Q, nullptr);
-        M.unit_done = unit_done.data();
+        M.unit_done = E.unit_done = unit_done.data();
         uint32_t nd = 0;
         for (uint32_t i = 0; i < n; i++) nd += unit_done[i] == 1u;
         err_out[3] = nd;
     }
+    if (o.crc && !fuse_xxh) {
+        hipemu::set_group(4);
+        kc_launch_xxh64(b.src, pl.rel_off.data(), n, xxh.data(), nullptr);
+        hipemu::set_group(64);
+    }
+    // the match finder over n_launch units (all, or the re-run's list), in the forced form
     std::vector<uint64_t> btab;
-    if (use_grp == 4) {  // SpeedBestCompression: kc_zbest_match_kernel on two persistent table slots, the bit costs from the device's own kernel
+    uint32_t bcur[2] = {0, 0};
+    int32_t bcost[96];
+    if (level == KC_SPEED_BEST) {  // two persistent table slots, the bit costs from the device's own kernel
         btab.assign((size_t)2 * (kc_zbest_table_bytes() / 8), 0);
-        uint32_t cur[2] = {0, 0};
-        int32_t cost[96];
-        memset(cost, 0, sizeof(cost));
-        kc_launch_zbest_cost(predef.data(), cost, nullptr);
-        kc_launch_zbest_match(M, btab.data(), cur, cost, n, 2, nullptr);
-    } else if (use_grp == 2) {  // SpeedDefault: kc_zdfast_match_grp_kernel, 8 lanes per unit
-        tables.assign((size_t)((n + 7) / 8 * 8) * (kc_zdfast_table_bytes() / 4), 0);
-        M.spec_w0 = 2; M.spec_grow = 2;
-        if (const char* e = getenv("KC_EMU_SPEC_W0")) M.spec_w0 = atoi(e);      // (tests: other speculation policies = other round shapes)
-        if (const char* e = getenv("KC_EMU_SPEC_GROW")) M.spec_grow = atoi(e);
-        hipemu::set_group(8);
-        kc_launch_zdfast_match_grp(M, tables.data(), n, nullptr);
-        hipemu::set_group(64);
-    } else if (use_grp == 3) {  // SpeedBetterCompression: kc_zbetter_match_grp_kernel, 16 lanes per unit, tables cleared (no stamps)
-        tables.assign((size_t)((n + 3) / 4 * 4) * (kc_zbetter_table_bytes() / 4), 0);
-        M.spec_w0 = 16; M.spec_grow = 0;
-        hipemu::set_group(16);
-        kc_launch_zbetter_match_grp(M, (uint8_t*)tables.data(), n, false, nullptr);
-        hipemu::set_group(64);
-    } else if (use_grp) {
-        tables.assign((size_t)((n + 7) / 8 * 8) << 15, 0);
-        M.spec_w0 = 1; M.spec_grow = 1; M.tuned = tuned; M.empty_filter = 1;
-        hipemu::set_group(8);
-        kc_launch_zfast_match_grp(M, tables.data(), n, nullptr);
-        hipemu::set_group(64);
-    } else {
-        M.spec_w0 = 16;
-        kc_launch_zfast_match_lds(M, nullptr, 0u, n, nullptr);
+        memset(bcost, 0, sizeof(bcost));
+        kc_launch_zbest_cost(predef.data(), bcost, nullptr);
     }
-    KcEntropyParams E;
-    memset(&E, 0, sizeof(E));
-    E.src = src; E.unit_off = unit_off; E.unit_blk0 = blk0.data(); E.seqs = seqs.data(); E.meta = meta.data(); E.lits = lits.data(); E.aux = aux.data();
-    E.stage = stage; E.stage_off = stage_off; E.out_size = out_size; E.xxh = xxh.data(); E.redo_mask = redo.data(); E.redo_blk = redo_blk.data();
-    E.predef = predef.data(); E.seq_stride = seq_stride; E.lit_stride = lit_stride; E.block_size = block_size; E.window_size = window;
-    E.crc = crc; E.single = single; E.no_entropy = entropy_opts & 1; E.all_lit_entropy = ((entropy_opts >> 1) & 1) | (use_grp >= 3 && use_grp <= 4 ? 1 : 0) /* allLitEntropy: levels above SpeedDefault */; E.full_zero = full_zero; E.stream_mode = stream_mode;
-    E.err_flag = err;
-    if (prescan) E.unit_done = unit_done.data();
-    if (fused_dst != nullptr) {  // the layout of kc_batch.cpp batch_end: raw payloads deferred, checksum behind the entropy stage
-        E.rawdef = rawdef.data();
-        E.unit_raw = unit_raw.data();
-        if (crc) E.xxh = nullptr;
-    }
-    kc_launch_zstd_entropy(E, n, nullptr);
-    if (fused_dst != nullptr) {
+    auto run_match = [&](uint32_t n_launch) {
+        const int lanes = level == KC_SPEED_BETTER ? 16 : 8;  // lanes per unit of the group kernels
+        if (level == KC_SPEED_BEST) {
+            kc_launch_zbest_match(M, btab.data(), bcur, bcost, n_launch, 2, nullptr);
+        } else if (level == KC_SPEED_FASTEST && !use_grp) {
+            KcMatchParams ml = M;
+            ml.spec_w0 = 16;
+            kc_launch_zfast_match_lds(ml, nullptr, 0u, n_launch, nullptr);
+        } else {
+            const uint32_t per_wave = 64 / lanes;
+            tables.assign((size_t)((n_launch + per_wave - 1) / per_wave * per_wave) * (zenc_table_bytes(level) / 4), 0);
+            hipemu::set_group(lanes);
+            if (level == KC_SPEED_DEFAULT) kc_launch_zdfast_match_grp(M, tables.data(), n_launch, nullptr);
+            else if (level == KC_SPEED_BETTER) kc_launch_zbetter_match_grp(M, (uint8_t*)tables.data(), n_launch, false, nullptr);
+            else {
+                KcMatchParams mf = M;
+                mf.tuned = tuned;
+                mf.empty_filter = 1;
+                kc_launch_zfast_match_grp(mf, tables.data(), n_launch, nullptr);
+            }
+            hipemu::set_group(64);
+        }
+    };
+    // batch_end's finishing pass: sizes -> offsets, checksum (+ payload of the raw-only frames), compaction
+    auto finish_pass = [&]() {
         kc_launch_scan_sizes(out_size, n, fused_off, nullptr);
-        if (crc) {
-            KcXxhFinParams X;
-            memset(&X, 0, sizeof(X));
-            X.src = src; X.unit_off = unit_off; X.n_units = n; X.stage = stage; X.stage_off = stage_off; X.out_size = out_size; X.out_off = fused_off;
-            X.dst = fused_dst; X.unit_raw = unit_raw.data(); X.rawdef = rawdef.data(); X.unit_blk0 = blk0.data(); X.xxh_out = xxh.data(); X.mode = fused_mode;
+        if (E.unit_raw != nullptr) {
+            const KcXxhFinParams X = zenc_xxh_fin_params(E, n, fused_off, fused_dst, xxh.data(), fused_mode);
             hipemu::set_group(4);
             kc_launch_xxh64_fin(X, nullptr);
             hipemu::set_group(64);
         }
-        kc_launch_compact(stage, stage_off, out_size, fused_off, fused_dst, n, nullptr, src, unit_off, blk0.data(), rawdef.data(), crc ? unit_raw.data() : nullptr);
+        kc_launch_compact(stage, E.stage_off, out_size, fused_off, fused_dst, n, nullptr, E.src, E.unit_off, E.unit_blk0, E.rawdef, E.unit_raw);
+    };
+    run_match(n);
+    kc_launch_zstd_entropy(E, n, nullptr);
+    if (fused_dst != nullptr) finish_pass();
+    uint32_t redo_units = 0;
+    const uint32_t max_passes = zenc_redo_max_passes(pl);
+    for (uint32_t iter = 0;; iter++) {
+        zenc_redo_units(redo.data(), n, list);
+        if (err[0] != 0 || list.empty()) break;
+        if (iter > max_passes) return -3;
+        zenc_redo_mark(pl, list, redo_blk.data(), pop_blk);
+        redo_units += (uint32_t)list.size();
+        std::fill(redo.begin(), redo.end(), 0u);
+        std::fill(redo_blk.begin(), redo_blk.end(), (uint8_t)0);
+        M.pop_blk = pop_blk.data();
+        M.unit_list = E.unit_list = list.data();
+        run_match((uint32_t)list.size());
+        kc_launch_zstd_entropy(E, (uint32_t)list.size(), nullptr);
+    }
+    if (redo_units != 0 && fused_dst != nullptr) finish_pass();
+    if (fuse_xxh) {
         uint32_t nraw = 0;
         for (uint32_t i = 0; i < n; i++) nraw += unit_raw[i];
         err_out[2] = nraw;
     }
-    uint32_t anyredo = 0;
-    for (uint32_t i = 0; i < n; i++) anyredo |= redo[i];
     err_out[0] = err[0];
-    err_out[1] = anyredo;  // (a unit that needs the speculation re-run: the host would run it again; the test picks inputs that do not)
+    err_out[1] = redo_units;
+    return 0;
+}
+
+// kcemu_zstd_batch under this export's earlier signature, which the test helpers of earlier revisions call: the level rides in use_grp (2 / 3 / 4),
+// block_size and window are given, and the frames go to the caller's own slots (stage_off), as far as a slot holds them.
+int kcemu_zstd_frames(const uint8_t* src, const uint64_t* unit_off, uint32_t n, int block_size, int window, int crc, int single, int full_zero,
+                      int stream_mode, int use_grp, int tuned, int entropy_opts, uint8_t* stage, const uint64_t* stage_off, uint32_t* out_size,
+                      uint32_t* err_out, uint8_t* fused_dst /* or null */, uint64_t* fused_off, int fused_mode) {
+    const int level = use_grp >= 2 ? use_grp : KC_SPEED_FASTEST;
+    std::vector<uint64_t> own_off(n + 1, 0);
+    auto call = [&](uint8_t* st, uint64_t cap) {
+        return kcemu_zstd_batch(src, unit_off, n, level, block_size, window, crc, single, full_zero, stream_mode, use_grp == 1, tuned, entropy_opts, nullptr,
+                                nullptr, st, cap, own_off.data(), out_size, err_out, fused_dst, fused_off, fused_mode);
+    };
+    if (int r = call(nullptr, 0)) return r;
+    std::vector<uint8_t> own((size_t)own_off[n] + 64, 0);
+    if (int r = call(own.data(), own_off[n])) return r;
+    for (uint32_t i = 0; i < n; i++)
+        memcpy(stage + stage_off[i], own.data() + own_off[i], (size_t)std::min<uint64_t>(out_size[i], stage_off[i + 1] - stage_off[i]));
     return 0;
 }
 

@@ -5,7 +5,7 @@ Host-side mirror of the klauspost/compress encoder API for the encode hot path
 include/kcgpu.h (libkcgpu.so: hand-written HIP kernels for gfx950).  There is no CPU
 fallback in this package: without the HIP library or a GPU every encode call raises.
 """
-from . import zstd, s2, flate, gzip  # noqa: F401
+from . import zstd, s2, flate, gzip, zlib  # noqa: F401
 from ._lib import KcError, lib_path, load as load_library  # noqa: F401
 
-__all__ = ["zstd", "s2", "flate", "gzip", "KcError", "lib_path", "load_library"]
+__all__ = ["zstd", "s2", "flate", "gzip", "zlib", "KcError", "lib_path", "load_library"]

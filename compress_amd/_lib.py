@@ -62,6 +62,7 @@ SYMBOLS = [
     "kc_flate_ropts_default", "kc_flate_ropts_free", "kc_flate_ropts_dict", "kc_flate_ropts_multistream",
     "kc_flate_inflate_dev", "kc_flate_inflate", "kc_flate_inflate_bound_dev", "kc_flate_inflate_bound",
     "kc_gzip_inflate_dev", "kc_gzip_inflate", "kc_gzip_inflate_bound_dev", "kc_gzip_inflate_bound",
+    "kc_zlib_inflate_dev", "kc_zlib_inflate", "kc_zlib_inflate_bound_dev", "kc_zlib_inflate_bound",
     "kc_probe_table_pattern", "kc_probe_pcie", "kc_ctx_trim", "kc_device_trim", "kc_s2_hook_declined", "kc_create_error", "kc_host_alloc", "kc_host_free",
 ]
 
@@ -284,11 +285,12 @@ def load():
     L.kc_flate_ropts_dict.restype = C.c_int
     L.kc_flate_ropts_multistream.argtypes = [vp, C.c_int]
     L.kc_flate_ropts_multistream.restype = C.c_int
-    for n in ("kc_flate_inflate_dev", "kc_flate_inflate", "kc_gzip_inflate_dev", "kc_gzip_inflate"):
+    for n in ("kc_flate_inflate_dev", "kc_flate_inflate", "kc_gzip_inflate_dev", "kc_gzip_inflate", "kc_zlib_inflate_dev", "kc_zlib_inflate"):
         f = getattr(L, n)
         f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, u64, vp, vp, vp]
         f.restype = C.c_int
-    for n in ("kc_flate_inflate_bound_dev", "kc_flate_inflate_bound", "kc_gzip_inflate_bound_dev", "kc_gzip_inflate_bound"):
+    for n in ("kc_flate_inflate_bound_dev", "kc_flate_inflate_bound", "kc_gzip_inflate_bound_dev", "kc_gzip_inflate_bound",
+              "kc_zlib_inflate_bound_dev", "kc_zlib_inflate_bound"):
         f = getattr(L, n)
         f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp]
         f.restype = C.c_int

@@ -1,12 +1,13 @@
 // kc_flate_api.cpp — flate.NewReader / flate.NewReaderDict / gzip.NewReader over a batch of independent inputs: the reader options
-// and the entry points kc_flate_inflate[_bound][_dev] / kc_gzip_inflate[_bound][_dev] of include/kcgpu.h.  The sequence of one
+// and the entry points kc_flate_inflate[_bound][_dev] / kc_gzip_inflate[_bound][_dev] / kc_zlib_inflate[_bound][_dev] of include/kcgpu.h.  The sequence of one
 // device call is kc_flate_host.h's; this file gives it the device (HipDevice over kc_ctx::fl), checks the arguments and serves
 // host buffers.
 #include "kc_decdev_hip.h"
 #include "kc_flate_host.h"
 
 struct kc_flate_ropts {
-    std::vector<uint8_t> dict;  // flate.NewReaderDict: its last 32 KiB
+    std::vector<uint8_t> dict;  // flate.NewReaderDict / zlib.NewReaderDict: its last 32 KiB
+    uint32_t dict_id = 1;       // adler32 of ALL its bytes (zlib's DICTID; adler32(nil) = 1)
     int multistream = 1;        // gzip.Reader.Multistream
 };
 
@@ -14,9 +15,9 @@ namespace {
 
 static_assert(FL_N == sizeof(kc_ctx::fl) / sizeof(DevBuf), "kc_ctx::fl has one slot per FL_* buffer");
 
-KcFlOpts opts_of(const kc_flate_ropts* o, bool gzip) {
+KcFlOpts opts_of(const kc_flate_ropts* o, uint32_t format) {
     KcFlOpts f;
-    f.gzip = gzip; f.multistream = o->multistream; f.dict = o->dict.data(); f.dict_len = (uint32_t)o->dict.size();
+    f.format = format; f.multistream = o->multistream; f.dict = o->dict.data(); f.dict_len = (uint32_t)o->dict.size(); f.dict_id = o->dict_id;
     return f;
 }
 
@@ -29,14 +30,14 @@ kc_status check_inflate_args(kc_ctx* c, const kc_flate_ropts* o, const void* src
     return !bound && n && !dst && dst_cap ? KC_ERR_BAD_ARG : KC_OK;
 }
 
-kc_status inflate_dev(kc_ctx* c, const kc_flate_ropts* o, bool gzip, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint8_t* d_dst,
+kc_status inflate_dev(kc_ctx* c, const kc_flate_ropts* o, uint32_t format, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint8_t* d_dst,
                       uint64_t dst_cap, uint64_t* out_off, uint32_t* status, uint64_t* consumed, uint64_t* bound) {
     kc_status s = check_inflate_args(c, o, d_src, in_off, n, d_dst, dst_cap, out_off, status, bound);
     if (s != KC_OK) return s;
     KcDecTimes T;
     if (n) HIPCHK(c, hipSetDevice(c->device));
     HipDevice dev(c, c->fl);
-    return take_outcome(c, T, kc_fl_inflate(&dev, opts_of(o, gzip), d_src, in_off, n, d_dst, dst_cap, out_off, status, consumed, bound, T),
+    return take_outcome(c, T, kc_fl_inflate(&dev, opts_of(o, format), d_src, in_off, n, d_dst, dst_cap, out_off, status, consumed, bound, T),
                         "dst_cap too small for the planned layout");
 }
 
@@ -99,7 +100,7 @@ kc_status host_sweeps(kc_ctx* c, KcDecDevice* dev, const KcFlOpts& o, const uint
     return KC_OK;
 }
 
-kc_status inflate_host(kc_ctx* c, const kc_flate_ropts* o, bool gzip, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst,
+kc_status inflate_host(kc_ctx* c, const kc_flate_ropts* o, uint32_t format, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst,
                        uint64_t dst_cap, uint64_t* out_off, uint32_t* status, uint64_t* consumed, uint64_t* bound) {
     kc_status s = check_inflate_args(c, o, src, in_off, n, dst, dst_cap, out_off, status, bound);
     if (s != KC_OK) return s;
@@ -109,7 +110,7 @@ kc_status inflate_host(kc_ctx* c, const kc_flate_ropts* o, bool gzip, const uint
     if (n == 0) return KC_OK;
     HIPCHK(c, hipSetDevice(c->device));
     HipDevice dev(c, c->fl);
-    return take_outcome(c, T, host_sweeps(c, &dev, opts_of(o, gzip), src, in_off, n, dst, dst_cap, out_off, status, consumed, bound, T),
+    return take_outcome(c, T, host_sweeps(c, &dev, opts_of(o, format), src, in_off, n, dst, dst_cap, out_off, status, consumed, bound, T),
                         "dst_cap too small for the planned layout");
 }
 
@@ -125,6 +126,7 @@ int kc_flate_ropts_dict(kc_flate_ropts* o, const uint8_t* bytes, uint64_t len) {
     if (!o || (len && !bytes)) return -1;
     const uint64_t keep = len > 32768 ? 32768 : len;
     try { o->dict.assign(bytes + (len - keep), bytes + len); } catch (...) { return -1; }
+    o->dict_id = kc_fl_adler32(bytes, len);  // zlib's DICTID is that of the whole dictionary (zlib/reader.go:164-165), not of the window's tail
     return 0;
 }
 int kc_flate_ropts_multistream(kc_flate_ropts* o, int b) {  // gzip.Reader.Multistream, gzip/gunzip.go:142-144
@@ -136,44 +138,67 @@ int kc_flate_ropts_multistream(kc_flate_ropts* o, int b) {  // gzip.Reader.Multi
 // io.ReadAll(flate.NewReaderDict(input, dict)) per input: flate/inflate.go:352-395, 464-597, 600-670, flate/inflate_gen.go
 kc_status kc_flate_inflate_dev(kc_ctx* c, const kc_flate_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint8_t* d_dst, uint64_t dst_cap,
                                uint64_t* out_off, uint32_t* status, uint64_t* consumed) {
-    return inflate_dev(c, o, false, d_src, in_off, n, d_dst, dst_cap, out_off, status, consumed, nullptr);
+    return inflate_dev(c, o, KCFL_FMT_FLATE, d_src, in_off, n, d_dst, dst_cap, out_off, status, consumed, nullptr);
 }
 kc_status kc_flate_inflate(kc_ctx* c, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst, uint64_t dst_cap,
                            uint64_t* out_off, uint32_t* status, uint64_t* consumed) {
-    return inflate_host(c, o, false, src, in_off, n, dst, dst_cap, out_off, status, consumed, nullptr);
+    return inflate_host(c, o, KCFL_FMT_FLATE, src, in_off, n, dst, dst_cap, out_off, status, consumed, nullptr);
 }
 kc_status kc_flate_inflate_bound_dev(kc_ctx* c, const kc_flate_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint64_t* bound,
                                      uint32_t* status, uint64_t* consumed) {
     if (n && !bound) return KC_ERR_BAD_ARG;
     uint64_t none = 0;
-    return inflate_dev(c, o, false, d_src, in_off, n, nullptr, 0, nullptr, status, consumed, n ? bound : &none);
+    return inflate_dev(c, o, KCFL_FMT_FLATE, d_src, in_off, n, nullptr, 0, nullptr, status, consumed, n ? bound : &none);
 }
 kc_status kc_flate_inflate_bound(kc_ctx* c, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint64_t* bound, uint32_t* status,
                                  uint64_t* consumed) {
     if (n && !bound) return KC_ERR_BAD_ARG;
     uint64_t none = 0;
-    return inflate_host(c, o, false, src, in_off, n, nullptr, 0, nullptr, status, consumed, n ? bound : &none);
+    return inflate_host(c, o, KCFL_FMT_FLATE, src, in_off, n, nullptr, 0, nullptr, status, consumed, n ? bound : &none);
 }
 // io.ReadAll(gzip.NewReader(input)) per input: gzip/gunzip.go:94-124, 183-295
 kc_status kc_gzip_inflate_dev(kc_ctx* c, const kc_flate_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint8_t* d_dst, uint64_t dst_cap,
                               uint64_t* out_off, uint32_t* status, uint64_t* consumed) {
-    return inflate_dev(c, o, true, d_src, in_off, n, d_dst, dst_cap, out_off, status, consumed, nullptr);
+    return inflate_dev(c, o, KCFL_FMT_GZIP, d_src, in_off, n, d_dst, dst_cap, out_off, status, consumed, nullptr);
 }
 kc_status kc_gzip_inflate(kc_ctx* c, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst, uint64_t dst_cap,
                           uint64_t* out_off, uint32_t* status, uint64_t* consumed) {
-    return inflate_host(c, o, true, src, in_off, n, dst, dst_cap, out_off, status, consumed, nullptr);
+    return inflate_host(c, o, KCFL_FMT_GZIP, src, in_off, n, dst, dst_cap, out_off, status, consumed, nullptr);
 }
 kc_status kc_gzip_inflate_bound_dev(kc_ctx* c, const kc_flate_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint64_t* bound,
                                     uint32_t* status, uint64_t* consumed) {
     if (n && !bound) return KC_ERR_BAD_ARG;
     uint64_t none = 0;
-    return inflate_dev(c, o, true, d_src, in_off, n, nullptr, 0, nullptr, status, consumed, n ? bound : &none);
+    return inflate_dev(c, o, KCFL_FMT_GZIP, d_src, in_off, n, nullptr, 0, nullptr, status, consumed, n ? bound : &none);
 }
 kc_status kc_gzip_inflate_bound(kc_ctx* c, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint64_t* bound, uint32_t* status,
                                 uint64_t* consumed) {
     if (n && !bound) return KC_ERR_BAD_ARG;
     uint64_t none = 0;
-    return inflate_host(c, o, true, src, in_off, n, nullptr, 0, nullptr, status, consumed, n ? bound : &none);
+    return inflate_host(c, o, KCFL_FMT_GZIP, src, in_off, n, nullptr, 0, nullptr, status, consumed, n ? bound : &none);
+}
+
+// io.ReadAll(zlib.NewReaderDict(input, dict)) per input, from a fresh reader: zlib/reader.go:84-91, 134-187 (the header, the
+// DICTID), :93-121 (the trailer)
+kc_status kc_zlib_inflate_dev(kc_ctx* c, const kc_flate_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint8_t* d_dst, uint64_t dst_cap,
+                              uint64_t* out_off, uint32_t* status, uint64_t* consumed) {
+    return inflate_dev(c, o, KCFL_FMT_ZLIB, d_src, in_off, n, d_dst, dst_cap, out_off, status, consumed, nullptr);
+}
+kc_status kc_zlib_inflate(kc_ctx* c, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst, uint64_t dst_cap,
+                          uint64_t* out_off, uint32_t* status, uint64_t* consumed) {
+    return inflate_host(c, o, KCFL_FMT_ZLIB, src, in_off, n, dst, dst_cap, out_off, status, consumed, nullptr);
+}
+kc_status kc_zlib_inflate_bound_dev(kc_ctx* c, const kc_flate_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint64_t* bound,
+                                    uint32_t* status, uint64_t* consumed) {
+    if (n && !bound) return KC_ERR_BAD_ARG;
+    uint64_t none = 0;
+    return inflate_dev(c, o, KCFL_FMT_ZLIB, d_src, in_off, n, nullptr, 0, nullptr, status, consumed, n ? bound : &none);
+}
+kc_status kc_zlib_inflate_bound(kc_ctx* c, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint64_t* bound, uint32_t* status,
+                                uint64_t* consumed) {
+    if (n && !bound) return KC_ERR_BAD_ARG;
+    uint64_t none = 0;
+    return inflate_host(c, o, KCFL_FMT_ZLIB, src, in_off, n, nullptr, 0, nullptr, status, consumed, n ? bound : &none);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 #pragma once
 #include "kc_dev.h"
 #include "kc_s2_dev.h"
+#include "kc_wave.h"
 
 // per-input verdicts: the KC_FL_* of include/kcgpu.h
 #define KCFL_OK 0u
@@ -25,6 +26,7 @@
 #define KCFL_HEADER 3u
 #define KCFL_CHECKSUM 4u
 #define KCFL_SIZE 5u
+#define KCFL_DICTIONARY 6u
 #define KCFL_RAW_EOF 100u  // internal: the raw io.EOF of inflate_gen.go:114-122, 142-151, 210-219 — ReadAll ends without an error
 #define KCFL_MAX_OUT ((uint64_t)1 << 30)  // decoded bytes per input this library serves
 
@@ -32,9 +34,9 @@ struct KcFlateParams {
     const uint8_t* src;          // the inputs, concatenated
     const uint64_t* in_off;      // n + 1
     uint32_t n;
-    uint32_t gzip;               // 0: raw DEFLATE; 1: gzip members
+    uint32_t gzip;               // 0: raw DEFLATE; 1: gzip members; 2: zlib (KCFL_FMT_*; the flate kernels see 0 or 1 only)
     uint32_t multistream;        // gzip.Reader.Multistream
-    const uint8_t* dict;         // the preset dictionary's last dict_len <= 32768 bytes (raw DEFLATE only)
+    const uint8_t* dict;         // the preset dictionary's last dict_len <= 32768 bytes (raw DEFLATE; zlib where the stream has FDICT)
     uint32_t dict_len;
     // sizing pass: written; write pass: read
     uint64_t* size;              // planned bytes: the whole input when it stands, else the gzip members complete in front of the error
@@ -45,9 +47,15 @@ struct KcFlateParams {
     const uint64_t* out0;        // where input i's range starts in dst
     uint8_t* dst;
     uint32_t* wstatus;           // the final verdict of every input the write pass ran for
+    uint32_t dict_id;            // zlib: the Adler-32 of the WHOLE preset dictionary (1 without one), what a DICTID is compared with
 };
+#define KCFL_FMT_FLATE 0u
+#define KCFL_FMT_GZIP 1u
+#define KCFL_FMT_ZLIB 2u
 void kc_launch_flate_size(const KcFlateParams& P, hipStream_t st);
 void kc_launch_flate_write(const KcFlateParams& P, hipStream_t st);
+void kc_launch_zlib_size(const KcFlateParams& P, hipStream_t st);
+void kc_launch_zlib_write(const KcFlateParams& P, hipStream_t st);
 
 #define KCFL_PB_L 10  // primary-table bits: literal/length, distance, code-length codes
 #define KCFL_PB_D 9
@@ -505,5 +513,101 @@ __device__ __forceinline__ uint32_t fl_input(const KcFlateParams& P, const uint6
         *size = O.d; *used = pos - begin; *n_members = done;
         if (!P.multistream) break;
     }
+    return KCFL_OK;
+}
+
+// ---- zlib (RFC 1950): zlib/reader.go:134-187 (Reset: the header), :93-121 (Read: the trailer) ----
+
+#define KCFL_ADLER_MOD 65521u
+#define KCFL_ADLER_CHUNK 16384u  // bytes the wave sums between two reductions: 256 per lane, whatever n is
+
+// The Adler-32 of ptr[0, n), wave-wide, of bytes this wave has written (KC_WAVE_SYNC before).  All lanes call and all get the value;
+// n = 0 gives 1.  With s1 = 1 + sum b[i] and s2 = n + sum (n - i) * b[i], a chunk of L bytes that holds the plain sum A and the
+// position-weighted sum W = sum k * b[k] (k from the chunk's start) moves the pair by s2 += L * s1 + L * A - W, s1 += A.
+// The range is read as the aligned words that cover it: it is taken to begin `mis` bytes earlier, at the word boundary, with bytes
+// of zero there that are never loaded; they add nothing to s1 and 1 each to s2, which starts that much lower.  Lane j takes the
+// words j, j + 64, ... of a chunk: 64 lanes, 64 consecutive words per round.  A first or last word that the range covers in part
+// is put together from its bytes inside the range.
+// Overflow, for the fixed chunk of 16384 bytes: a lane sums 64 words = 256 bytes per chunk, so its plain sum is at most
+// 256 * 255 = 65 280 and its weighted sum at most 255 * 256 * 16383 < 1.07e9 < 2^32.  The weighted sums are taken mod 65521 in
+// the lanes before they are added up (64 * 65520 < 2^23; unreduced, 255 * 16384^2 / 2 would pass 2^32); the chunk's plain sum is
+// at most 16384 * 255 < 2^22.  The scalar update is 64-bit: L * s1 + L * A <= 16384 * (65520 + 4 177 920) < 2^36.
+__device__ __forceinline__ uint32_t fl_adler32_wave(const uint8_t* ptr, const uint64_t n, const int lane) {
+    const uint32_t mis = (uint32_t)((uintptr_t)ptr & 3u);
+    const uint8_t* q = ptr - mis;          // word-aligned; q[v] is in the range for mis <= v < total
+    const uint64_t total = n + mis;
+    uint32_t s1 = 1, s2 = KCFL_ADLER_MOD - mis;
+    // every round takes a chunk: KCFL_ADLER_CHUNK bytes, or the rest
+    for (uint64_t c0 = 0; c0 < total; c0 += KCFL_ADLER_CHUNK) {
+        const uint32_t L = total - c0 < KCFL_ADLER_CHUNK ? (uint32_t)(total - c0) : KCFL_ADLER_CHUNK;
+        const uint8_t* c = q + c0;
+        uint32_t a = 0, w = 0;
+        auto add = [&](const uint32_t k, const uint32_t x) {
+            const uint32_t b0 = x & 0xFFu, b1 = (x >> 8) & 0xFFu, b2 = (x >> 16) & 0xFFu, b3 = x >> 24;
+            const uint32_t sum = b0 + b1 + b2 + b3;
+            a += sum;
+            w += k * sum + b1 + 2u * b2 + 3u * b3;
+        };
+        if (L == KCFL_ADLER_CHUNK && (c0 || !mis)) {  // a whole chunk inside the range: 64 words per lane
+#pragma unroll 8
+            for (uint32_t j = 0; j < KCFL_ADLER_CHUNK / 256u; j++) {
+                const uint32_t k = 4u * ((uint32_t)lane + 64u * j);
+                add(k, ld32(c + k));
+            }
+        } else {
+            // every round takes this lane's next word of the chunk, 256 bytes on
+            for (uint32_t k = 4u * (uint32_t)lane; k < L; k += 256u) {
+                uint32_t x = 0;
+                if (c0 + k >= mis && k + 4u <= L) x = ld32(c + k);
+                else
+                    for (uint32_t t = 0; t < 4u; t++)
+                        if (c0 + k + t >= mis && k + t < L) x |= (uint32_t)c[k + t] << (8u * t);
+                add(k, x);
+            }
+        }
+        const uint32_t A = wave_reduce_sum(a), W = wave_reduce_sum(w % KCFL_ADLER_MOD);
+        s2 = (uint32_t)(((uint64_t)s2 + (uint64_t)L * s1 + (uint64_t)L * A + 64u * KCFL_ADLER_MOD - W) % KCFL_ADLER_MOD);
+        s1 = (s1 + A) % KCFL_ADLER_MOD;
+    }
+    return (s2 % KCFL_ADLER_MOD) << 16 | s1;
+}
+
+// One zlib input, as io.ReadAll(zlib.NewReaderDict(input, dict)) from a fresh reader: the two header bytes, the DICTID against
+// P.dict_id, the DEFLATE stream, and the big-endian Adler-32 behind the byte that holds its last bit; what follows is not read.
+// The verdict short of / with the Adler-32 (the write pass computes it); *size and *used as KcFlateParams describes them.
+// (A reader that is REUSED hands its dictionary to the decompressor even without FDICT, reader.go:177-179: not modelled, there is
+// no reused reader here.)
+template <bool WRITE>
+__device__ __forceinline__ uint32_t fl_zlib_input(const KcFlateParams& P, const uint64_t begin, const uint64_t end, uint8_t* dst, const uint64_t cap,
+                                                  FlLds& L, uint64_t* size, uint64_t* used, const int lane) {
+    *size = 0; *used = 0;
+    const uint8_t* s = P.src;
+    if (end - begin < 2) return KCFL_EOF;                                      // reader.go:143-149
+    const uint32_t cmf = uniu((uint32_t)s[begin]), flg = uniu((uint32_t)s[begin + 1]);
+    if ((cmf & 0x0Fu) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31u) return KCFL_HEADER;   // :150-154
+    uint64_t p = begin + 2;
+    const bool have_dict = flg & 0x20u;
+    if (have_dict) {                                                           // :155-169
+        if (end - p < 4) return KCFL_EOF;
+        if (__builtin_bswap32(uniu(ld32(s + p))) != P.dict_id) return KCFL_DICTIONARY;
+        p += 4;
+    }
+    FlBits B;
+    B.src = s; B.end = end;
+    FlOut O;
+    O.dst = dst; O.cap = cap; O.d = 0; O.hist = P.dict; O.hist_len = have_dict ? P.dict_len : 0; O.base = 0; O.nlit = 0; O.lit = 0;
+    fl_seek(B, p);
+    uint32_t e = fl_inflate<WRITE>(B, O, L, lane);
+    fl_flush<WRITE>(O, lane);
+    if (e == KCFL_RAW_EOF) e = KCFL_OK;  // the stream "ends" at the input's end: the trailer read below then finds nothing
+    if (e) return e;
+    p = fl_read_pos(B);
+    if (end - p < 4) return KCFL_EOF;                                          // :107-113
+    const uint32_t want = __builtin_bswap32(uniu(ld32(s + p)));
+    if (WRITE) {
+        KC_WAVE_SYNC();
+        if (uniu(fl_adler32_wave(O.dst, O.d, lane)) != want) return KCFL_CHECKSUM;   // :115-119
+    }
+    *size = O.d; *used = p + 4 - begin;
     return KCFL_OK;
 }

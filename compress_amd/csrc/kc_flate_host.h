@@ -1,10 +1,10 @@
 #pragma once
-// kc_flate_host.h — host side of flate.NewReader / flate.NewReaderDict / gzip.NewReader over a batch of independent inputs, written
+// kc_flate_host.h — host side of flate.NewReader / flate.NewReaderDict / gzip.NewReader / zlib.NewReaderDict over a batch of independent inputs, written
 // against KcDecDevice alone (kc_flate_api.cpp runs it on the device, tools/hipemu/kcemu.cpp on the wave emulator over plain memory).
 //
-// One call: the sizing pass (kc_flate_inflate.hip) walks every input and yields its decoded size, its verdict short of the CRC-32
+// One call: the sizing pass (kc_flate_inflate.hip) walks every input and yields its decoded size, its verdict short of the checksum
 // and the bytes it read; the prefix sum of the sizes IS the output layout; the write pass decodes every input straight to its
-// place, checks the gzip CRCs and zero-fills what failed.  Nothing is staged and nothing is compacted, and no scratch grows with
+// place, checks the gzip CRCs / the zlib Adler-32 and zero-fills what failed.  Nothing is staged and nothing is compacted, and no scratch grows with
 // the inputs' bytes: the device form is one batch whatever the budget.
 #include <stdint.h>
 #include <string.h>
@@ -16,11 +16,24 @@
 enum { FL_IN_OFF, FL_SIZE, FL_STATUS, FL_CONSUMED, FL_MEMBERS, FL_OUT0, FL_WSTATUS, FL_DICT, FL_N };
 
 struct KcFlOpts {
-    bool gzip = false;
+    uint32_t format = KCFL_FMT_FLATE;  // KCFL_FMT_*: raw DEFLATE, gzip or zlib
     int multistream = 1;            // gzip.Reader.Multistream
-    const uint8_t* dict = nullptr;  // flate.NewReaderDict: its last dict_len <= 32 KiB (raw DEFLATE only)
+    const uint8_t* dict = nullptr;  // flate.NewReaderDict / zlib.NewReaderDict: its last dict_len <= 32 KiB (not read for gzip)
     uint32_t dict_len = 0;
+    uint32_t dict_id = 1;           // zlib: adler32 of the WHOLE dictionary (adler32(nil) = 1), zlib/reader.go:164-165
 };
+
+// adler32.Checksum (RFC 1950, section 8.2), plain: the dictionary's id is computed once, on the host
+static inline uint32_t kc_fl_adler32(const uint8_t* p, uint64_t n) {
+    uint32_t s1 = 1, s2 = 0;
+    while (n) {  // 5552 bytes of 0xFF are the most that 32-bit sums hold between two reductions
+        const uint64_t k = n < 5552 ? n : 5552;
+        for (uint64_t i = 0; i < k; i++) { s1 += p[i]; s2 += s1; }
+        s1 %= 65521u; s2 %= 65521u;
+        p += k; n -= k;
+    }
+    return s2 << 16 | s1;
+}
 
 // the sizing pass's results on the host, and the parameters both passes share (the arrays of the inputs last prepared)
 struct KcFlPlan {
@@ -45,9 +58,10 @@ static inline int kc_fl_prepare(KcDecDevice* dev, const KcFlOpts& o, const uint8
     P.src = d_src;
     P.in_off = d_in_off;
     P.n = n;
-    P.gzip = o.gzip;
+    P.gzip = o.format;
     P.multistream = o.multistream != 0;
-    if (!o.gzip && o.dict_len) {
+    P.dict_id = o.dict_id;
+    if (o.format != KCFL_FMT_GZIP && o.dict_len) {
         uint8_t* d_dict = nullptr;
         if ((s = kc_dec_reserve(dev, FL_DICT, o.dict_len, &d_dict)) || (s = dev->h2d(d_dict, o.dict, o.dict_len))) return s;
         P.dict = d_dict;
@@ -63,7 +77,8 @@ static inline int kc_fl_size_inputs(KcDecDevice* dev, KcFlPlan& H, uint32_t at, 
     const uint32_t n = P.n;
     int s;
     if ((s = dev->mark(0))) return s;
-    kc_launch_flate_size(P, dev->stream);
+    if (P.gzip == KCFL_FMT_ZLIB) kc_launch_zlib_size(P, dev->stream);
+    else kc_launch_flate_size(P, dev->stream);
     if ((s = dev->mark(1)) || (s = dev->d2h(H.size.data() + at, P.size, (size_t)n * 8)) || (s = dev->d2h(H.status.data() + at, P.status, (size_t)n * 4)) ||
         (s = dev->d2h(H.consumed.data() + at, P.consumed, (size_t)n * 8)) || (s = dev->d2h(H.members.data() + at, P.members, (size_t)n * 4)) ||
         (s = dev->sync()))
@@ -86,7 +101,8 @@ static inline int kc_fl_write_inputs(KcDecDevice* dev, const KcFlPlan& H, uint32
     P.dst = d_dst;
     std::vector<uint32_t> wst(n);
     if ((s = dev->h2d(H.d_out0, out0, (size_t)n * 8)) || (s = dev->mark(1))) return s;
-    kc_launch_flate_write(P, dev->stream);
+    if (P.gzip == KCFL_FMT_ZLIB) kc_launch_zlib_write(P, dev->stream);
+    else kc_launch_flate_write(P, dev->stream);
     if ((s = dev->mark(2)) || (s = dev->d2h(wst.data(), P.wstatus, (size_t)n * 4)) || (s = dev->sync())) return s;
     T.match_ms += dev->span(1, 2);
     for (uint32_t i = 0; i < n; i++) {

@@ -5,7 +5,9 @@ import ctypes as C
 from . import _lib
 
 FL_OK, FL_CORRUPT, FL_EOF, FL_HEADER, FL_CHECKSUM, FL_SIZE_EXCEEDED = 0, 1, 2, 3, 4, 5
-FL_NAMES = {0: "KC_FL_OK", 1: "KC_FL_CORRUPT", 2: "KC_FL_EOF", 3: "KC_FL_HEADER", 4: "KC_FL_CHECKSUM", 5: "KC_FL_SIZE_EXCEEDED"}
+FL_DICTIONARY = 6
+FL_NAMES = {0: "KC_FL_OK", 1: "KC_FL_CORRUPT", 2: "KC_FL_EOF", 3: "KC_FL_HEADER", 4: "KC_FL_CHECKSUM", 5: "KC_FL_SIZE_EXCEEDED",
+            6: "KC_FL_DICTIONARY"}
 
 
 class InflateError(ValueError):

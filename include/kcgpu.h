@@ -609,13 +609,13 @@ uint64_t kc_s2_rstream_skip_left(const kc_s2_rstream* s);
 kc_status kc_s2_rstream_on_skippable(kc_s2_rstream* s, uint8_t id, kc_s2_skippable_fn fn, void* user);
 kc_status kc_s2_rstream_reset(kc_s2_rstream* s);
 void kc_s2_rstream_free(kc_s2_rstream* s);
-/* ---- flate.NewReader / gzip.NewReader over a batch of independent inputs (inflate) ----
- * Raw DEFLATE (RFC 1951) and gzip (RFC 1952), whole inputs, ONE WAVE PER INPUT: zip members, gzip members, BGZF blocks, HTTP
+/* ---- flate.NewReader / gzip.NewReader / zlib.NewReader over a batch of independent inputs (inflate) ----
+ * Raw DEFLATE (RFC 1951), gzip (RFC 1952) and zlib (RFC 1950), whole inputs, ONE WAVE PER INPUT: zip members, gzip members, BGZF blocks, HTTP
  * bodies, PNG IDAT runs.  No sizes are supplied: a sizing pass walks every input and yields its exact decoded size before any byte
  * is written, the prefix sum of the sizes is the output layout, and a write pass decodes every input straight to its place.
  * Options: kc_flate_ropts_default returns a new object with the reference's defaults (no dictionary, multistream on);
  * kc_flate_ropts_dict == flate.NewReaderDict (flate/inflate.go:948-957): ONE preset dictionary per call, of which the last 32 KiB
- * count (the window); it is read by the flate entry points only.  kc_flate_ropts_multistream == gzip.Reader.Multistream
+ * count (the window) and all bytes make zlib's DICTID; it is read by the flate and zlib entry points.  kc_flate_ropts_multistream == gzip.Reader.Multistream
  * (gzip/gunzip.go:126-144), read by the gzip entry points only.  Both return 0, -1 on a null object. */
 typedef struct kc_flate_ropts kc_flate_ropts;
 kc_flate_ropts* kc_flate_ropts_default(void);
@@ -629,9 +629,10 @@ enum {
     KC_FL_EOF = 2,            /* io.ErrUnexpectedEOF; also a gzip input of zero bytes, for which gzip.NewReader returns io.EOF */
     KC_FL_HEADER = 3,         /* gzip.ErrHeader */
     KC_FL_CHECKSUM = 4,       /* gzip.ErrChecksum: CRC-32 or ISIZE */
-    KC_FL_SIZE_EXCEEDED = 5   /* a limit of this library, the one deviation from the reference: an input that decodes to more than 1 GiB,
+    KC_FL_SIZE_EXCEEDED = 5,  /* a limit of this library, the one deviation from the reference: an input that decodes to more than 1 GiB,
                                  or (host-buffer forms) one whose input bytes plus decoded bytes are above a quarter of the context's
                                  scratch budget (KC_OPT_MAX_SCRATCH_MIB, and 85 % of what is free) */
+    KC_FL_DICTIONARY = 6      /* zlib.ErrDictionary: the stream names a preset dictionary other than the call's (zlib/reader.go:164-168) */
 };
 /* kc_flate_inflate[_dev] == io.ReadAll(flate.NewReaderDict(bytes.NewReader(input), dict)) for every input (flate/inflate.go:352-395
  * nextBlock, :464-597 readHuffman, :600-670 dataBlock / copyData, :116-176 huffmanDecoder.init, :740-783 huffSym;
@@ -684,6 +685,29 @@ kc_status kc_gzip_inflate(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* s
 kc_status kc_gzip_inflate_bound_dev(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n,
                                     uint64_t* bound, uint32_t* status, uint64_t* consumed);
 kc_status kc_gzip_inflate_bound(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n,
+                                uint64_t* bound, uint32_t* status, uint64_t* consumed);
+/* kc_zlib_inflate[_dev] == io.ReadAll(zlib.NewReaderDict(bytes.NewReader(input), dict)) for every input, each from a FRESH reader
+ * (zlib/reader.go:84-91 NewReaderDict, :134-187 Reset: the header, :93-121 Read: the trailer): zlib streams (RFC 1950) such as PNG
+ * IDAT runs, git objects, PDF streams, HTTP `deflate` bodies.  Arguments and output as above; kc_flate_ropts_dict gives the preset
+ * dictionary, multistream is not read.
+ * Fewer than 2 bytes: KC_FL_EOF (:143-149).  CM other than 8, CINFO above 7 or a header not divisible by 31: KC_FL_HEADER (:150-154).
+ * With FDICT four more bytes are needed (KC_FL_EOF) and are compared, big-endian, with the Adler-32 of the WHOLE dictionary given
+ * to kc_flate_ropts_dict — not of the 32 KiB the window keeps —: KC_FL_DICTIONARY when they differ (:155-169).  Without a dictionary
+ * the value compared with is adler32(nil) = 1, so a stream with FDICT and DICTID 1 is accepted and decoded without history, as in the
+ * reference.  Without FDICT the dictionary is ignored (:171-176).  The reference hands the dictionary to a REUSED decompressor even
+ * without FDICT (Reset, :177-179); that is not modelled: every input has a fresh reader, and so has compress_amd.zlib's Reader.Reset.
+ * The DEFLATE stream is decoded as for kc_flate_inflate, divergence and raw io.EOF included (the trailer is then missing: KC_FL_EOF).
+ * Four bytes follow the byte that holds the stream's last bit (fewer: KC_FL_EOF, :107-113): the big-endian Adler-32 of the decoded
+ * bytes.  The write pass computes it wave-wide over what it wrote; a mismatch is KC_FL_CHECKSUM (:115-119) and leaves the planned
+ * range zero-filled; every other failure leaves an empty range.  Bytes behind the trailer are ignored — there is no second member —
+ * and consumed[i] runs through the trailer.  kc_zlib_inflate_bound[_dev]: the sizing pass alone, every verdict short of the Adler-32. */
+kc_status kc_zlib_inflate_dev(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint8_t* d_dst,
+                              uint64_t dst_cap, uint64_t* out_off, uint32_t* status, uint64_t* consumed);
+kc_status kc_zlib_inflate(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst,
+                          uint64_t dst_cap, uint64_t* out_off, uint32_t* status, uint64_t* consumed);
+kc_status kc_zlib_inflate_bound_dev(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n,
+                                    uint64_t* bound, uint32_t* status, uint64_t* consumed);
+kc_status kc_zlib_inflate_bound(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n,
                                 uint64_t* bound, uint32_t* status, uint64_t* consumed);
 
 /* Single-block form with the WriterCustomEncoder contract (s2/writer.go:1053-1064): no varint header;

@@ -216,7 +216,17 @@ int kcemu_flate_inflate(const uint8_t* src, const uint64_t* in_off, uint32_t n, 
 int kcemu_gzip_inflate(const uint8_t* src, const uint64_t* in_off, uint32_t n, int multistream, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off,
                        uint64_t* bound, uint32_t* status, uint64_t* consumed) {
     KcFlOpts o;
-    o.gzip = true; o.multistream = multistream;
+    o.format = KCFL_FMT_GZIP; o.multistream = multistream;
+    return kcemu_flate(o, src, in_off, n, dst, dst_cap, out_off, bound, status, consumed);
+}
+// N x io.ReadAll(zlib.NewReaderDict(input, dict)): the id from the whole dictionary, the window's tail to the device
+int kcemu_zlib_inflate(const uint8_t* src, const uint64_t* in_off, uint32_t n, const uint8_t* dict, uint32_t dict_len, uint8_t* dst, uint64_t dst_cap,
+                       uint64_t* out_off, uint64_t* bound, uint32_t* status, uint64_t* consumed) {
+    KcFlOpts o;
+    o.format = KCFL_FMT_ZLIB;
+    o.dict_id = kc_fl_adler32(dict, dict_len);
+    if (dict_len > 32768) { dict += dict_len - 32768; dict_len = 32768; }
+    o.dict = dict; o.dict_len = dict_len;
     return kcemu_flate(o, src, in_off, n, dst, dst_cap, out_off, bound, status, consumed);
 }
 

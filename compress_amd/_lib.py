@@ -63,6 +63,8 @@ SYMBOLS = [
     "kc_flate_inflate_dev", "kc_flate_inflate", "kc_flate_inflate_bound_dev", "kc_flate_inflate_bound",
     "kc_gzip_inflate_dev", "kc_gzip_inflate", "kc_gzip_inflate_bound_dev", "kc_gzip_inflate_bound",
     "kc_zlib_inflate_dev", "kc_zlib_inflate", "kc_zlib_inflate_bound_dev", "kc_zlib_inflate_bound",
+    "kc_flate_wopts_default", "kc_flate_wopts_free", "kc_flate_wopts_level", "kc_flate_wopts_end", "kc_flate_wopts_block",
+    "kc_flate_deflate_bound", "kc_flate_deflate_dev", "kc_flate_deflate", "kc_gzip_deflate_dev", "kc_gzip_deflate",
     "kc_probe_table_pattern", "kc_probe_pcie", "kc_ctx_trim", "kc_device_trim", "kc_s2_hook_declined", "kc_create_error", "kc_host_alloc", "kc_host_free",
 ]
 
@@ -293,6 +295,22 @@ def load():
               "kc_zlib_inflate_bound_dev", "kc_zlib_inflate_bound"):
         f = getattr(L, n)
         f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp]
+        f.restype = C.c_int
+    L.kc_flate_wopts_default.argtypes = []
+    L.kc_flate_wopts_default.restype = vp
+    L.kc_flate_wopts_free.argtypes = [vp]
+    L.kc_flate_wopts_free.restype = None
+    L.kc_flate_wopts_level.argtypes = [vp, C.c_int]
+    L.kc_flate_wopts_level.restype = C.c_int
+    L.kc_flate_wopts_end.argtypes = [vp, C.c_int]
+    L.kc_flate_wopts_end.restype = C.c_int
+    L.kc_flate_wopts_block.argtypes = [vp, C.c_uint32, C.c_uint32]
+    L.kc_flate_wopts_block.restype = C.c_int
+    L.kc_flate_deflate_bound.argtypes = [u64, C.c_uint32]
+    L.kc_flate_deflate_bound.restype = u64
+    for n in ("kc_flate_deflate_dev", "kc_flate_deflate", "kc_gzip_deflate_dev", "kc_gzip_deflate"):
+        f = getattr(L, n)
+        f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, u64, vp]
         f.restype = C.c_int
     L.kc_s2_encode_block.argtypes = [vp, vp, u64, vp, u64]
     L.kc_s2_encode_block.restype = C.c_int64

@@ -1,5 +1,6 @@
-"""compress/flate's reader on the device: raw DEFLATE (RFC 1951) inflated in batches of independent inputs, one wave per input
-(include/kcgpu.h kc_flate_inflate*; kernels compress_amd/csrc/kc_flate_inflate.hip).  There is no CPU fallback."""
+"""compress/flate on the device: raw DEFLATE (RFC 1951) inflated in batches of independent inputs, one wave per input
+(include/kcgpu.h kc_flate_inflate*; kernels compress_amd/csrc/kc_flate_inflate.hip), and written at flate.HuffmanOnly, the one level
+with a device writer (kc_flate_deflate*; kc_flate_deflate.hip: the writer is at the end of this file).  There is no CPU fallback."""
 import ctypes as C
 
 from . import _lib
@@ -226,3 +227,156 @@ def NewReader(r, device=0):
 def NewReaderDict(r, dict, device=0):
     """flate.NewReaderDict(r, dict): only the dictionary's last 32 KiB count."""
     return Reader(r, dict, device=device)
+
+
+# ---- the writer: flate.NewWriter(w, flate.HuffmanOnly) on the device (include/kcgpu.h kc_flate_deflate*; kernels
+# compress_amd/csrc/kc_flate_deflate.hip).  HuffmanOnly is the one level with a device writer; there is no CPU fallback. ----
+HuffmanOnly = -2
+ConstantCompression = HuffmanOnly  # flate/deflate.go:31-38: the older name of the same level
+
+
+class WriteBatch:
+    """The batch entry points of one writer format over one options object and one device context (gzip.py shares it).
+    block / penalty: the two values compressor.init fixes per level (deflate.go:795-799); None keeps HuffmanOnly's 32768 and 10."""
+
+    def __init__(self, prefix, level=HuffmanOnly, flush=False, block=None, penalty=None, device=0, stream=None):
+        L = _lib.load()
+        self._prefix = prefix
+        self._o = C.c_void_p(L.kc_flate_wopts_default())
+        if not self._o:
+            raise MemoryError("kc_flate_wopts_default")
+        rc = L.kc_flate_wopts_level(self._o, int(level))
+        if rc != 0:
+            raise _lib.KcError(rc, "flate: level %d has no device writer (flate.HuffmanOnly, -2, is the one served)" % level)
+        rc = L.kc_flate_wopts_end(self._o, 1 if flush else 0)
+        if rc == 0 and (block is not None or penalty is not None):
+            rc = L.kc_flate_wopts_block(self._o, 32768 if block is None else int(block), 10 if penalty is None else int(penalty))
+        if rc != 0:
+            raise _lib.KcError(rc, "flate: writer options rejected")
+        self.block = 32768 if block is None else int(block)
+        self._device, self._stream, self._ctx = device, stream, None
+
+    def ctx(self):
+        if self._ctx is None:
+            self._ctx = _lib.Context(self._device, self._stream)
+        return self._ctx
+
+    def bound(self, in_off):
+        """The capacity that holds any output of these inputs (kc_flate_deflate_bound per input; gzip adds 18)."""
+        L = _lib.load()
+        extra = 18 if "gzip" in self._prefix else 0
+        return sum(int(L.kc_flate_deflate_bound(int(in_off[i + 1] - in_off[i]), self.block)) + extra for i in range(len(in_off) - 1))
+
+    def deflate(self, src_ptr, in_off, dst_ptr, dst_cap, dev):
+        """One call of the C entry point: uint64[n + 1] out_off.  Raises KcError KC_ERR_DST_TOO_SMALL when the exact total is above
+        dst_cap (`.out_off` of the error holds the layout of the device form)."""
+        import numpy as np
+        ctx = self.ctx()
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = len(in_off) - 1
+        out_off = np.zeros(n + 1, dtype=np.uint64)
+        fn = getattr(ctx.L, self._prefix + ("_dev" if dev else ""))
+        try:
+            ctx.check(fn(ctx.h, self._o, src_ptr, in_off.ctypes.data, n, dst_ptr, int(dst_cap), out_off.ctypes.data))
+        except _lib.KcError as e:
+            e.out_off = out_off
+            raise
+        return out_off
+
+    def all_host(self, src, in_off):
+        """The host-buffer form into a buffer of this call's own, sized by the bound: a list of bytes, one per input."""
+        import numpy as np
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        if len(src) == 0:
+            src = np.zeros(1, dtype=np.uint8)
+        in_off = np.ascontiguousarray(in_off, dtype=np.uint64)
+        n = len(in_off) - 1
+        cap = self.bound(in_off)
+        dst = np.empty(cap + 64, dtype=np.uint8)
+        out_off = self.deflate(src.ctypes.data, in_off, dst.ctypes.data, cap, False)
+        return [dst[int(out_off[i]):int(out_off[i + 1])].tobytes() for i in range(n)]
+
+    def close(self):
+        c, self._ctx = self._ctx, None
+        if c is not None:
+            c.close()
+
+    def __del__(self):
+        try:
+            self.close()
+            if getattr(self, "_o", None):
+                _lib.load().kc_flate_wopts_free(self._o)
+                self._o = None
+        except Exception:
+            pass
+
+
+def DeflateBound(n, block=32768):
+    """kc_flate_deflate_bound: the most bytes an input of n bytes becomes."""
+    return int(_lib.load().kc_flate_deflate_bound(int(n), int(block)))
+
+
+def DeflateAll(src, in_off, level=HuffmanOnly, flush=False, device=0, block=None, penalty=None):
+    """N x (w = flate.NewWriter(buf, level); w.Write(input_i); w.Close()) in one batch, byte for byte; flush=True: w.Flush() in
+    Close's place (the stream stays open).  src: numpy uint8 (host), the inputs concatenated; in_off: uint64[n + 1].  Returns a list
+    of bytes.  level: flate.HuffmanOnly only (KcError KC_ERR_UNSUPPORTED otherwise)."""
+    b = WriteBatch("kc_flate_deflate", level, flush, block, penalty, device=device)
+    try:
+        return b.all_host(src, in_off)
+    finally:
+        b.close()
+
+
+def DeflateAllDevice(d_src_ptr, in_off, d_dst_ptr, dst_cap, level=HuffmanOnly, flush=False, device=0, stream=None, block=None, penalty=None):
+    """Device-resident form (pointers are ints): returns uint64[n + 1] offsets into d_dst (host numpy).  Raises KcError
+    KC_ERR_DST_TOO_SMALL when the exact total is above dst_cap: nothing is written, and the error's .out_off holds the layout."""
+    b = WriteBatch("kc_flate_deflate", level, flush, block, penalty, device=device, stream=stream)
+    try:
+        return b.deflate(d_src_ptr, in_off, d_dst_ptr, dst_cap, True)
+    finally:
+        b.close()
+
+
+class Writer:
+    """flate.NewWriter(w, level) (deflate.go:890-897) as a writer object: Write, Close, Reset.
+
+    Write buffers; Close encodes everything written as ONE input on the device and writes the stream to w.  Flush in mid-stream
+    would need the writer's state kept across device calls and is not served: it raises."""
+
+    _prefix = "kc_flate_deflate"
+
+    def __init__(self, w, level=HuffmanOnly, device=0):
+        if level != HuffmanOnly:
+            raise _lib.KcError(_lib.KC_ERR_UNSUPPORTED, "flate: level %d has no device writer (flate.HuffmanOnly, -2, is the one served)" % level)
+        self._level, self._device = level, device
+        self.Reset(w)
+
+    def Reset(self, w):
+        """Writer.Reset (deflate.go:998-1023): what was buffered is dropped; write to w from now on."""
+        self._w, self._buf, self._closed = w, bytearray(), False
+
+    def Write(self, p):
+        if self._closed:
+            raise ValueError("flate: write to closed writer")
+        self._buf += bytes(p)
+        return len(p)
+
+    def Flush(self):
+        raise NotImplementedError("flate: Writer.Flush in mid-stream is not served on the device; DeflateAll(flush=True) ends a whole input with a flush")
+
+    def Close(self):
+        if self._closed:
+            return
+        import numpy as np
+        b = WriteBatch(self._prefix, self._level, False, device=self._device)
+        try:
+            out = b.all_host(np.frombuffer(bytes(self._buf), dtype=np.uint8), np.array([0, len(self._buf)], dtype=np.uint64))[0]
+        finally:
+            b.close()
+        self._closed, self._buf = True, bytearray()
+        self._w.write(out)
+
+
+def NewWriter(w, level=HuffmanOnly, device=0):
+    """flate.NewWriter(w, level)."""
+    return Writer(w, level, device=device)

@@ -121,3 +121,37 @@ class Reader(flate.Reader):
 def NewReader(r, device=0):
     """gzip.NewReader(r)."""
     return Reader(r, device=device)
+
+
+# ---- the writer: gzip.NewWriterLevel(w, gzip.HuffmanOnly) on the device (include/kcgpu.h kc_gzip_deflate*) ----
+HuffmanOnly = flate.HuffmanOnly
+
+
+def GzipAll(src, in_off, level=HuffmanOnly, flush=False, device=0, block=None, penalty=None):
+    """N x (w = gzip.NewWriterLevel(buf, level); w.Write(input_i); w.Close()) in one batch, byte for byte: the default Header (no
+    name, no time, OS 255), the HuffmanOnly stream, CRC-32 and size.  flush=True: w.Flush() in Close's place — no trailer."""
+    b = flate.WriteBatch("kc_gzip_deflate", level, flush, block, penalty, device=device)
+    try:
+        return b.all_host(src, in_off)
+    finally:
+        b.close()
+
+
+def GzipAllDevice(d_src_ptr, in_off, d_dst_ptr, dst_cap, level=HuffmanOnly, flush=False, device=0, stream=None, block=None, penalty=None):
+    """Device-resident form: uint64[n + 1] offsets into d_dst (see flate.DeflateAllDevice)."""
+    b = flate.WriteBatch("kc_gzip_deflate", level, flush, block, penalty, device=device, stream=stream)
+    try:
+        return b.deflate(d_src_ptr, in_off, d_dst_ptr, dst_cap, True)
+    finally:
+        b.close()
+
+
+class Writer(flate.Writer):
+    """gzip.Writer (gzip.go:32-47) with the default Header: Write buffers, Close encodes one input on the device."""
+
+    _prefix = "kc_gzip_deflate"
+
+
+def NewWriterLevel(w, level=HuffmanOnly, device=0):
+    """gzip.NewWriterLevel(w, level): gzip.HuffmanOnly is the one level served."""
+    return Writer(w, level, device=device)

@@ -710,6 +710,52 @@ kc_status kc_zlib_inflate_bound_dev(kc_ctx* ctx, const kc_flate_ropts* o, const 
 kc_status kc_zlib_inflate_bound(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n,
                                 uint64_t* bound, uint32_t* status, uint64_t* consumed);
 
+/* ---- flate.NewWriter / gzip.NewWriterLevel at flate.HuffmanOnly over a batch of independent inputs (deflate) ----
+ * The output of every input is, byte for byte, what flate.NewWriter(w, flate.HuffmanOnly); Write(input); Close() writes
+ * (flate/deflate.go:755-770 write, :701-708 storeHuff, :865-880 close; flate/huffman_bit_writer.go:987-1174 writeBlockHuff,
+ * :269-348 generateCodegen, :458-497 writeDynamicHeader, :502-529 writeStoredHeader; flate/huffman_code.go:339-371 generate,
+ * :183-309 bitCounts).  The level has no match finder and no history: blocks depend on each other only through the table in force
+ * and the bit position, so the device works BY BLOCK — a plan kernel (histogram, candidate table, header; one wave per block), a
+ * chain kernel (the stored / reuse / new-table decisions in order; one wave per input) and an emit kernel (one wave per block).
+ * Options: kc_flate_wopts_default returns a new object at HuffmanOnly with the reference's values.
+ * kc_flate_wopts_level: -2 (flate.HuffmanOnly) is the one level served; any other is KC_ERR_UNSUPPORTED (levels 0, 1 - 9 and the
+ * custom windows have no device writer).  kc_flate_wopts_end: KC_FL_END_CLOSE (the default; Close, :865-880) or KC_FL_END_FLUSH
+ * (Flush in Close's place, syncFlush :772-785: the stream ends with an empty stored block and stays open; gzip then has no trailer).
+ * kc_flate_wopts_block(bytes, penalty): the two values compressor.init fixes per level (:787-827) — the window that becomes one
+ * block (32768 at HuffmanOnly; 1 .. 65535) and logNewTablePenalty (10 at HuffmanOnly; 0 .. 31).  (65535, 8) reproduces the
+ * reference's own goldens of writeBlockHuff (flate/testdata/huffman-*.golden).  KC_ERR_BAD_ARG outside these ranges. */
+typedef struct kc_flate_wopts kc_flate_wopts;
+enum { KC_FL_END_CLOSE = 0, KC_FL_END_FLUSH = 1 };
+kc_flate_wopts* kc_flate_wopts_default(void);
+void kc_flate_wopts_free(kc_flate_wopts* o);
+kc_status kc_flate_wopts_level(kc_flate_wopts* o, int level);
+kc_status kc_flate_wopts_end(kc_flate_wopts* o, int end);
+kc_status kc_flate_wopts_block(kc_flate_wopts* o, uint32_t bytes, uint32_t penalty);
+/* The most bytes one input of len bytes becomes at the given block size, in closed form (0: block outside 1 .. 65535); gzip adds
+ * 18.  Per block its bytes and 176, and 8 for the stream's end.  Stored framing (5 bytes a block) is NOT the worst case: a Huffman
+ * block is chosen against the reference's 560-bit GUESS of its header (:1009, :1036-1046), while a real header may reach
+ * 17 + 19*3 + 258*7 = 1880 bits, and an EOB owed to the table before and the block's own add 30. */
+uint64_t kc_flate_deflate_bound(uint64_t len, uint32_t block);
+/* src: the inputs, concatenated; in_off: n + 1 ascending offsets; dst / dst_cap: the output; out_off[n + 1]: host array in both
+ * forms.  The _dev forms take device pointers for src and dst.  Output: out_off is dense — input i owns dst[out_off[i],
+ * out_off[i + 1]), its exact size.  An empty input is the ten-bit fixed block alone (:513-518).  KC_ERR_DST_TOO_SMALL when the
+ * exact total is above dst_cap: nothing is written beyond dst_cap (the _dev forms: nothing at all, and out_off holds the layout —
+ * out_off[n] is the capacity to come back with).  KC_ERR_UNSUPPORTED: an input above 1 GiB, or one whose block records alone
+ * exceed the context's scratch budget.  The _dev forms cut a batch into groups of inputs whose block records fit the scratch budget
+ * (about 2 KiB per block; a call of several groups plans each group twice).  The host-buffer forms stage groups of inputs whose bytes
+ * and bound together stay within half of the budget; they do not use the rolling host pipeline. */
+kc_status kc_flate_deflate_dev(kc_ctx* ctx, const kc_flate_wopts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint8_t* d_dst,
+                               uint64_t dst_cap, uint64_t* out_off);
+kc_status kc_flate_deflate(kc_ctx* ctx, const kc_flate_wopts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst,
+                           uint64_t dst_cap, uint64_t* out_off);
+/* gzip.NewWriterLevel(w, gzip.HuffmanOnly); Write(input); Close() for every input (gzip/gzip.go:171-243 Write: the header, :264-290
+ * Close: the trailer): the default Header only — 1f 8b 08 00, MTIME 0, XFL 0 at this level, OS 255 —, the stream as above, CRC-32
+ * and the size modulo 2^32, little-endian.  With KC_FL_END_FLUSH (gzip.Writer.Flush, :245-262) the trailer is missing. */
+kc_status kc_gzip_deflate_dev(kc_ctx* ctx, const kc_flate_wopts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n, uint8_t* d_dst,
+                              uint64_t dst_cap, uint64_t* out_off);
+kc_status kc_gzip_deflate(kc_ctx* ctx, const kc_flate_wopts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst,
+                          uint64_t dst_cap, uint64_t* out_off);
+
 /* Single-block form with the WriterCustomEncoder contract (s2/writer.go:1053-1064): no varint header;
  * returns bytes used, 0 = incompressible (store raw), <0 = fall back to the built-in encoder.
  * "The function should expect to be called concurrently" (writer.go:1058; s2.Writer calls it from one goroutine per block,

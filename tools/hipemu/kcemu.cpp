@@ -27,10 +27,12 @@
 #include "../../compress_amd/csrc/kc_s2_rstream.hip"
 #include "../../compress_amd/csrc/kc_s2rstream_host.h"
 #include "../../compress_amd/csrc/kc_flate_inflate.hip"
+#include "../../compress_amd/csrc/kc_flate_deflate.hip"
 
 #include "../../compress_amd/csrc/kc_s2dec_host.h"
 #include "../../compress_amd/csrc/kc_s2ranges_host.h"
 #include "../../compress_amd/csrc/kc_flate_host.h"
+#include "../../compress_amd/csrc/kc_deflate_host.h"
 #include "../../compress_amd/csrc/kc_zstd_opts.cpp"  // (host code: the encoder's option functions)
 #include "../../compress_amd/csrc/kc_zenc_host.h"    // (host code: the rules of the zstd encode batch)
 
@@ -229,6 +231,28 @@ int kcemu_zlib_inflate(const uint8_t* src, const uint64_t* in_off, uint32_t n, c
     o.dict = dict; o.dict_len = dict_len;
     return kcemu_flate(o, src, in_off, n, dst, dst_cap, out_off, bound, status, consumed);
 }
+
+// N x (flate.NewWriter(w, HuffmanOnly); Write(input); Close() -- or Flush() with end = 1): kc_deflate_host.h's sequence over plain
+// memory, at the block size and penalty given (compressor.init's 32768 and 10).  Returns 0, -2 when dst_cap is below the exact total
+// (out_off holds the layout, nothing is written), -4 for an input whose records exceed the scratch budget.
+static int kcemu_deflate(uint32_t gzip, const uint8_t* src, const uint64_t* in_off, uint32_t n, int end, uint32_t block, uint32_t penalty, uint8_t* dst,
+                         uint64_t dst_cap, uint64_t* out_off) {
+    KcDfOpts o;
+    o.gzip = gzip; o.end = end ? KCDF_END_FLUSH : KCDF_END_CLOSE; o.block = block; o.penalty = penalty;
+    KcemuDevice dev;
+    g_last = KcDecTimes();
+    return kc_df_deflate(&dev, o, src, in_off, n, dst, dst_cap, out_off, g_last);
+}
+int kcemu_flate_deflate(const uint8_t* src, const uint64_t* in_off, uint32_t n, int end, uint32_t block, uint32_t penalty, uint8_t* dst, uint64_t dst_cap,
+                        uint64_t* out_off) {
+    return kcemu_deflate(0, src, in_off, n, end, block, penalty, dst, dst_cap, out_off);
+}
+// N x (gzip.NewWriterLevel(w, HuffmanOnly); Write(input); Close() -- or Flush())
+int kcemu_gzip_deflate(const uint8_t* src, const uint64_t* in_off, uint32_t n, int end, uint32_t block, uint32_t penalty, uint8_t* dst, uint64_t dst_cap,
+                       uint64_t* out_off) {
+    return kcemu_deflate(1, src, in_off, n, end, block, penalty, dst, dst_cap, out_off);
+}
+uint64_t kcemu_flate_deflate_bound(uint64_t len, uint32_t block) { return kc_df_bound(len, block); }
 
 // s2.ReadSeeker.ReadAt over m requests: kc_s2ranges_host.h's layout, Index.Find and sequence over plain memory.  Returns 0, -2 when
 // dst_cap is too small (nothing written), -1 for a request that names no input or wraps.

@@ -65,6 +65,8 @@ SYMBOLS = [
     "kc_zlib_inflate_dev", "kc_zlib_inflate", "kc_zlib_inflate_bound_dev", "kc_zlib_inflate_bound",
     "kc_flate_wopts_default", "kc_flate_wopts_free", "kc_flate_wopts_level", "kc_flate_wopts_end", "kc_flate_wopts_block",
     "kc_flate_deflate_bound", "kc_flate_deflate_dev", "kc_flate_deflate", "kc_gzip_deflate_dev", "kc_gzip_deflate",
+    "kc_flate_swopts_default", "kc_flate_swopts_free", "kc_flate_swopts_eof", "kc_flate_swopts_dict", "kc_flate_stateless_bound",
+    "kc_flate_stateless_deflate_dev", "kc_flate_stateless_deflate", "kc_gzip_stateless_deflate_dev", "kc_gzip_stateless_deflate",
     "kc_probe_table_pattern", "kc_probe_pcie", "kc_ctx_trim", "kc_device_trim", "kc_s2_hook_declined", "kc_create_error", "kc_host_alloc", "kc_host_free",
 ]
 
@@ -309,6 +311,20 @@ def load():
     L.kc_flate_deflate_bound.argtypes = [u64, C.c_uint32]
     L.kc_flate_deflate_bound.restype = u64
     for n in ("kc_flate_deflate_dev", "kc_flate_deflate", "kc_gzip_deflate_dev", "kc_gzip_deflate"):
+        f = getattr(L, n)
+        f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, u64, vp]
+        f.restype = C.c_int
+    L.kc_flate_swopts_default.argtypes = []
+    L.kc_flate_swopts_default.restype = vp
+    L.kc_flate_swopts_free.argtypes = [vp]
+    L.kc_flate_swopts_free.restype = None
+    L.kc_flate_swopts_eof.argtypes = [vp, C.c_int]
+    L.kc_flate_swopts_eof.restype = C.c_int
+    L.kc_flate_swopts_dict.argtypes = [vp, C.c_char_p, u64]
+    L.kc_flate_swopts_dict.restype = C.c_int
+    L.kc_flate_stateless_bound.argtypes = [u64, u64]
+    L.kc_flate_stateless_bound.restype = u64
+    for n in ("kc_flate_stateless_deflate_dev", "kc_flate_stateless_deflate", "kc_gzip_stateless_deflate_dev", "kc_gzip_stateless_deflate"):
         f = getattr(L, n)
         f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, u64, vp]
         f.restype = C.c_int

@@ -29,6 +29,7 @@ struct KcDecDevice {
 // What a batch decoder's sequence reports besides its results.
 struct KcDecTimes {
     float prep_ms = 0, match_ms = 0, other_ms = 0;  // plan passes / decode / checksum and compaction
+    float emit_ms = 0;                              // the stateless writers' emit kernel (kc_stateless_host.h), reported as kc_timings::entropy_ms
     int batches = 0;                                // device batches the call was cut into
     uint64_t max_need = 0;                          // the largest single input's scratch, 1/8 allowance included: the least budget that refuses nothing
 };

@@ -76,10 +76,11 @@ __device__ __forceinline__ uint32_t df_reverse(uint32_t code, uint32_t n) {
     return r;
 }
 
-// what generate needs besides its inputs; one wave
+// what generate needs besides its inputs; one wave.  Sized for the largest alphabet generate is called on: the 286 literal / length
+// symbols of kc_flate_stateless.hip (the HuffmanOnly kernels use 257 of them).
 struct DfGenLds {
-    uint16_t rank[260];
-    uint16_t lit[260], frq[260];  // the nodes in order of (freq, literal), maxNode behind them
+    uint16_t rank[292];
+    uint16_t lit[292], frq[292];  // the nodes in order of (freq, literal), maxNode behind them
     int32_t lv[17][4];            // levelInfo: lastFreq, nextCharFreq, nextPairFreq, needed (level is the index)
     int32_t leaf[16][16];         // leafCounts
     int32_t bit_count[16];

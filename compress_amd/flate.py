@@ -380,3 +380,126 @@ class Writer:
 def NewWriter(w, level=HuffmanOnly, device=0):
     """flate.NewWriter(w, level)."""
     return Writer(w, level, device=device)
+
+
+# ---- the stateless writer: flate.StatelessDeflate / flate.NewStatelessWriter on the device (include/kcgpu.h kc_flate_stateless_*;
+# kernels compress_amd/csrc/kc_flate_stateless.hip): the reference's one LZ77 writer whose blocks are found independently.  It is not a
+# level of NewWriter, in the reference or here.  There is no CPU fallback. ----
+class StatelessBatch(WriteBatch):
+    """The batch entry points of the stateless writers over one options object and one device context (gzip.py shares it)."""
+
+    def __init__(self, prefix="kc_flate_stateless_deflate", eof=True, dict=None, device=0, stream=None):
+        L = _lib.load()
+        # every field close() and __del__ look at stands before anything can raise
+        self._prefix, self._device, self._stream, self._ctx, self._o = prefix, device, stream, None, None
+        self._o = C.c_void_p(L.kc_flate_swopts_default())
+        if not self._o:
+            raise MemoryError("kc_flate_swopts_default")
+        dict = bytes(dict) if dict else b""
+        rc = L.kc_flate_swopts_eof(self._o, 1 if eof else 0)
+        if rc == 0 and dict:
+            rc = L.kc_flate_swopts_dict(self._o, dict, len(dict))
+        if rc != 0:
+            raise _lib.KcError(rc, "flate: stateless writer options rejected")
+        self._dict_len = 0 if "gzip" in prefix else len(dict)
+
+    def bound(self, in_off):
+        """The capacity that holds any output of these inputs (kc_flate_stateless_bound per input; gzip adds 20)."""
+        L = _lib.load()
+        extra = 20 if "gzip" in self._prefix else 0
+        return sum(int(L.kc_flate_stateless_bound(int(in_off[i + 1] - in_off[i]), self._dict_len)) + extra for i in range(len(in_off) - 1))
+
+    def __del__(self):
+        try:
+            self.close()
+            if getattr(self, "_o", None):
+                _lib.load().kc_flate_swopts_free(self._o)
+                self._o = None
+        except Exception:
+            pass
+
+
+def StatelessBound(n, dict_len=0):
+    """kc_flate_stateless_bound: the most bytes an input of n bytes becomes behind a dictionary of dict_len bytes."""
+    return int(_lib.load().kc_flate_stateless_bound(int(n), int(dict_len)))
+
+
+def StatelessDeflateAll(src, in_off, eof=True, dict=None, device=0):
+    """N x flate.StatelessDeflate(buf, input_i, eof, dict) in one batch, byte for byte.  src: numpy uint8 (host), the inputs
+    concatenated; in_off: uint64[n + 1]; dict: one dictionary for the whole call (its last 8192 bytes count).  Returns a list of
+    bytes.  eof=False: every stream ends with an empty stored block and stays open."""
+    b = StatelessBatch("kc_flate_stateless_deflate", eof, dict, device=device)
+    try:
+        return b.all_host(src, in_off)
+    finally:
+        b.close()
+
+
+def StatelessDeflateAllDevice(d_src_ptr, in_off, d_dst_ptr, dst_cap, eof=True, dict=None, device=0, stream=None):
+    """Device-resident form (pointers are ints): returns uint64[n + 1] offsets into d_dst (host numpy).  Raises KcError
+    KC_ERR_DST_TOO_SMALL when the exact total is above dst_cap: nothing is written, and the error's .out_off holds the layout."""
+    b = StatelessBatch("kc_flate_stateless_deflate", eof, dict, device=device, stream=stream)
+    try:
+        return b.deflate(d_src_ptr, in_off, d_dst_ptr, dst_cap, True)
+    finally:
+        b.close()
+
+
+def _one(batch, data):
+    import numpy as np
+    data = bytes(data)
+    return batch.all_host(np.frombuffer(data, dtype=np.uint8), np.array([0, len(data)], dtype=np.uint64))[0]
+
+
+def StatelessDeflate(out, data, eof, dict=None, device=0):
+    """flate.StatelessDeflate(out, in, eof, dict) (stateless.go:76-162): one input, written to out."""
+    b = StatelessBatch("kc_flate_stateless_deflate", eof, dict, device=device)
+    try:
+        out.write(_one(b, data))
+    finally:
+        b.close()
+
+
+class StatelessWriter:
+    """flate.NewStatelessWriter(w) (stateless.go:21-55): every Write is one non-eof StatelessDeflate on the device, written to w at
+    once; Close is the eof call on nothing.  Nothing of the stream is kept between the calls, so the sizes of the Writes shape the
+    output.  The object keeps one device context for all its Writes; Close releases it."""
+
+    def __init__(self, w, device=0):
+        self._device, self._batch = device, None
+        self.Reset(w)
+
+    def Reset(self, w):
+        self._w, self._closed = w, False
+
+    def _write_call(self, p):
+        if self._batch is None:
+            self._batch = StatelessBatch("kc_flate_stateless_deflate", False, None, device=self._device)
+        self._w.write(_one(self._batch, p))
+
+    def _release(self):
+        b, self._batch = self._batch, None
+        if b is not None:
+            b.close()
+
+    def Write(self, p):
+        self._write_call(p)
+        return len(p)
+
+    def Close(self):
+        if self._closed:
+            return
+        self._closed = True
+        self._release()
+        StatelessDeflate(self._w, b"", True, None, device=self._device)
+
+    def __del__(self):
+        try:
+            self._release()
+        except Exception:
+            pass
+
+
+def NewStatelessWriter(w, device=0):
+    """flate.NewStatelessWriter(w)."""
+    return StatelessWriter(w, device=device)

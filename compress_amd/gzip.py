@@ -123,14 +123,25 @@ def NewReader(r, device=0):
     return Reader(r, device=device)
 
 
-# ---- the writer: gzip.NewWriterLevel(w, gzip.HuffmanOnly) on the device (include/kcgpu.h kc_gzip_deflate*) ----
+# ---- the writers: gzip.NewWriterLevel(w, gzip.HuffmanOnly) and (w, gzip.StatelessCompression) on the device (include/kcgpu.h
+# kc_gzip_deflate*, kc_gzip_stateless_deflate*) ----
 HuffmanOnly = flate.HuffmanOnly
+StatelessCompression = -3  # gzip/gzip.go:26-31: every Write one flate.StatelessDeflate, nothing kept between them
+
+
+def _batch(level, flush, block, penalty, device, stream=None):
+    if level == StatelessCompression:
+        if flush or block is not None or penalty is not None:
+            raise flate._lib.KcError(flate._lib.KC_ERR_UNSUPPORTED, "gzip: StatelessCompression has no flush ending, block size or penalty (Flush does nothing at this level)")
+        return flate.StatelessBatch("kc_gzip_stateless_deflate", device=device, stream=stream)
+    return flate.WriteBatch("kc_gzip_deflate", level, flush, block, penalty, device=device, stream=stream)
 
 
 def GzipAll(src, in_off, level=HuffmanOnly, flush=False, device=0, block=None, penalty=None):
     """N x (w = gzip.NewWriterLevel(buf, level); w.Write(input_i); w.Close()) in one batch, byte for byte: the default Header (no
-    name, no time, OS 255), the HuffmanOnly stream, CRC-32 and size.  flush=True: w.Flush() in Close's place — no trailer."""
-    b = flate.WriteBatch("kc_gzip_deflate", level, flush, block, penalty, device=device)
+    name, no time, OS 255), the stream, CRC-32 and size.  level: gzip.HuffmanOnly or gzip.StatelessCompression (KcError
+    KC_ERR_UNSUPPORTED otherwise).  flush=True (HuffmanOnly): w.Flush() in Close's place — no trailer."""
+    b = _batch(level, flush, block, penalty, device)
     try:
         return b.all_host(src, in_off)
     finally:
@@ -139,7 +150,7 @@ def GzipAll(src, in_off, level=HuffmanOnly, flush=False, device=0, block=None, p
 
 def GzipAllDevice(d_src_ptr, in_off, d_dst_ptr, dst_cap, level=HuffmanOnly, flush=False, device=0, stream=None, block=None, penalty=None):
     """Device-resident form: uint64[n + 1] offsets into d_dst (see flate.DeflateAllDevice)."""
-    b = flate.WriteBatch("kc_gzip_deflate", level, flush, block, penalty, device=device, stream=stream)
+    b = _batch(level, flush, block, penalty, device, stream)
     try:
         return b.deflate(d_src_ptr, in_off, d_dst_ptr, dst_cap, True)
     finally:
@@ -152,6 +163,43 @@ class Writer(flate.Writer):
     _prefix = "kc_gzip_deflate"
 
 
+class StatelessWriter(flate.StatelessWriter):
+    """gzip.Writer at StatelessCompression (gzip.go:171-235 Write, :264-290 Close): the header goes out with the first Write, every
+    Write is one non-eof flate.StatelessDeflate on the device, Close is the eof call on nothing, then CRC-32 and size.  Flush does
+    nothing at this level (:249-251)."""
+
+    _HEADER = bytes([0x1F, 0x8B, 8, 0, 0, 0, 0, 0, 0, 0xFF])
+
+    def Reset(self, w):
+        self._w, self._closed, self._wrote_header, self._crc, self._size = w, False, False, 0, 0
+
+    def Write(self, p):
+        import zlib as host_zlib
+        if self._closed:
+            raise ValueError("gzip: write to closed writer")
+        p = bytes(p)
+        if not self._wrote_header:
+            self._wrote_header = True
+            self._w.write(self._HEADER)
+        self._size = (self._size + len(p)) & 0xFFFFFFFF
+        self._crc = host_zlib.crc32(p, self._crc) & 0xFFFFFFFF
+        self._write_call(p)
+        return len(p)
+
+    def Flush(self):
+        return None
+
+    def Close(self):
+        if self._closed:
+            return
+        if not self._wrote_header:
+            self.Write(b"")
+        flate.StatelessWriter.Close(self)
+        self._w.write(self._crc.to_bytes(4, "little") + self._size.to_bytes(4, "little"))
+
+
 def NewWriterLevel(w, level=HuffmanOnly, device=0):
-    """gzip.NewWriterLevel(w, level): gzip.HuffmanOnly is the one level served."""
+    """gzip.NewWriterLevel(w, level): gzip.HuffmanOnly and gzip.StatelessCompression are the levels served."""
+    if level == StatelessCompression:
+        return StatelessWriter(w, device=device)
     return Writer(w, level, device=device)

@@ -756,6 +756,53 @@ kc_status kc_gzip_deflate_dev(kc_ctx* ctx, const kc_flate_wopts* o, const uint8_
 kc_status kc_gzip_deflate(kc_ctx* ctx, const kc_flate_wopts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst,
                           uint64_t dst_cap, uint64_t* out_off);
 
+/* ---- flate.StatelessDeflate / gzip.NewWriterLevel(w, gzip.StatelessCompression) over a batch of independent inputs ----
+ * The output of every input is, byte for byte, what flate.StatelessDeflate(out, input, eof, dict) writes (flate/stateless.go:76-162;
+ * statelessEnc :176-325; flate/token.go:212-309; flate/huffman_bit_writer.go:620-765 writeBlockDynamic, :824-975 writeTokens,
+ * :987-1174 writeBlockHuff): the one LZ77 writer of the reference whose blocks are found independently of each other.  The input is
+ * cut at fixed places — the first block 32767 - len(dict) bytes, every later one 24575 behind 8192 bytes of history that are the
+ * input's own — and every block has a fresh 8192-entry table, so the device works BY BLOCK: match (one wave per block, the table in
+ * LDS, tokens to scratch), plan (one wave per block: the block's tables, header and sizes), chain (one wave per input: stored /
+ * fixed / reuse / new table, the owed EOBs, in the reference's order) and emit (one wave per block).  The bit writer is the
+ * reference's pooled one, so logNewTablePenalty is 0: the estimate of a new table is doubled (:665, :1042).  tokens.EstimatedBits is
+ * float32 arithmetic; the value reproduced is that of the reference's default amd64 build (nothing fused).  This is not a level of
+ * flate.NewWriter in the reference either: kc_flate_wopts_level keeps refusing everything but -2.
+ * Options: kc_flate_swopts_default returns a new object with eof = 1 and no dictionary.  kc_flate_swopts_eof(0): the non-eof call —
+ * the stream ends with an empty stored block and stays open (one Write of flate.NewStatelessWriter).  kc_flate_swopts_dict: one
+ * dictionary for the whole call, copied; only its last 8192 bytes count, as in the reference (:93-95). */
+typedef struct kc_flate_swopts kc_flate_swopts;
+kc_flate_swopts* kc_flate_swopts_default(void);
+void kc_flate_swopts_free(kc_flate_swopts* o);
+kc_status kc_flate_swopts_eof(kc_flate_swopts* o, int eof);
+kc_status kc_flate_swopts_dict(kc_flate_swopts* o, const uint8_t* dict, uint64_t len);
+/* The most bytes one input of len bytes becomes behind a dictionary of dict_len bytes, in closed form; gzip adds 20 (header 10,
+ * trailer 8, the two bytes of Close's eof call).  Per block its bytes and 176, and 8 for the stream's end.  A block without a match
+ * is stored (5 bytes and an owed EOB).  A dynamic, reused-table or fixed block is never taken where stored is not larger:
+ * writeBlockDynamic compares exact sizes with the stored size before it writes (:731, :745; under a table in force :684, :698, where
+ * the size is the estimate newSize when a new table wins — then nothing is written there but a fixed block that is below it, and
+ * the exact comparison at :745 follows).  kc_last_timings after a call: match_ms the match kernel, prep_ms plan, other_ms chain,
+ * entropy_ms emit.  A Huffman-only block is writeBlockHuff's and inherits the 176
+ * bytes of kc_flate_deflate_bound (its header is chosen against a 560-bit guess).  Blocks: 0 for an empty input, 1 up to
+ * 32767 - min(dict_len, 8192) bytes, then one per 24575. */
+uint64_t kc_flate_stateless_bound(uint64_t len, uint64_t dict_len);
+/* Conventions as for kc_flate_deflate[_dev]: in_off[n + 1], a dense out_off, KC_ERR_DST_TOO_SMALL with the exact layout and (the
+ * _dev forms) nothing written, KC_ERR_UNSUPPORTED for an input above 1 GiB or one whose scratch alone exceeds the budget.  The
+ * scratch is about 2.5 KiB per block and FOUR bytes of tokens per input byte (with a dictionary 32 KiB per input more); the _dev
+ * forms cut a batch into groups of inputs that fit the budget (a call of several groups runs match, plan and chain twice per
+ * group).  An empty input with eof is the ten-bit fixed block alone (03 00); without eof the empty stored block (00 00 00 ff ff). */
+kc_status kc_flate_stateless_deflate_dev(kc_ctx* ctx, const kc_flate_swopts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n,
+                                         uint8_t* d_dst, uint64_t dst_cap, uint64_t* out_off);
+kc_status kc_flate_stateless_deflate(kc_ctx* ctx, const kc_flate_swopts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst,
+                                     uint64_t dst_cap, uint64_t* out_off);
+/* gzip.NewWriterLevel(w, gzip.StatelessCompression); Write(input); Close() for every input (gzip/gzip.go:171-235, :264-290): the
+ * default header (1f 8b 08 00, MTIME 0, XFL 0, OS 255), one non-eof StatelessDeflate of the input — its blocks and 00 00 ff ff from the
+ * next byte —, Close's eof call on nothing (the ten-bit fixed block, 03 00), CRC-32 and the size modulo 2^32.  eof and the dictionary
+ * of the options do not apply: the reference's gzip writer passes false and nil. */
+kc_status kc_gzip_stateless_deflate_dev(kc_ctx* ctx, const kc_flate_swopts* o, const uint8_t* d_src, const uint64_t* in_off, uint32_t n,
+                                        uint8_t* d_dst, uint64_t dst_cap, uint64_t* out_off);
+kc_status kc_gzip_stateless_deflate(kc_ctx* ctx, const kc_flate_swopts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n, uint8_t* dst,
+                                    uint64_t dst_cap, uint64_t* out_off);
+
 /* Single-block form with the WriterCustomEncoder contract (s2/writer.go:1053-1064): no varint header;
  * returns bytes used, 0 = incompressible (store raw), <0 = fall back to the built-in encoder.
  * "The function should expect to be called concurrently" (writer.go:1058; s2.Writer calls it from one goroutine per block,

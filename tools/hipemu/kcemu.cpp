@@ -28,11 +28,13 @@
 #include "../../compress_amd/csrc/kc_s2rstream_host.h"
 #include "../../compress_amd/csrc/kc_flate_inflate.hip"
 #include "../../compress_amd/csrc/kc_flate_deflate.hip"
+#include "../../compress_amd/csrc/kc_flate_stateless.hip"
 
 #include "../../compress_amd/csrc/kc_s2dec_host.h"
 #include "../../compress_amd/csrc/kc_s2ranges_host.h"
 #include "../../compress_amd/csrc/kc_flate_host.h"
 #include "../../compress_amd/csrc/kc_deflate_host.h"
+#include "../../compress_amd/csrc/kc_stateless_host.h"
 #include "../../compress_amd/csrc/kc_zstd_opts.cpp"  // (host code: the encoder's option functions)
 #include "../../compress_amd/csrc/kc_zenc_host.h"    // (host code: the rules of the zstd encode batch)
 
@@ -253,6 +255,21 @@ int kcemu_gzip_deflate(const uint8_t* src, const uint64_t* in_off, uint32_t n, i
     return kcemu_deflate(1, src, in_off, n, end, block, penalty, dst, dst_cap, out_off);
 }
 uint64_t kcemu_flate_deflate_bound(uint64_t len, uint32_t block) { return kc_df_bound(len, block); }
+
+// N x flate.StatelessDeflate(out, input, eof, dict) -- or, with gzip, N x (gzip.NewWriterLevel(w, StatelessCompression); Write(input);
+// Close()): kc_stateless_host.h's sequence over plain memory.  counts: KCSL_N_COUNTS decision counters of the call.  Returns 0, -2
+// when dst_cap is below the exact total (out_off holds the layout, nothing is written), -4 for an input beyond the scratch budget.
+int kcemu_flate_stateless(uint32_t gzip, const uint8_t* src, const uint64_t* in_off, uint32_t n, int eof, const uint8_t* dict, uint64_t dict_len,
+                          uint8_t* dst, uint64_t dst_cap, uint64_t* out_off, uint32_t* counts) {
+    KcSlOpts o;
+    o.gzip = gzip; o.eof = eof ? 1u : 0u;
+    if (dict_len > KCSL_MAX_DICT) { dict += dict_len - KCSL_MAX_DICT; dict_len = KCSL_MAX_DICT; }
+    if (dict_len && !gzip) o.dict.assign(dict, dict + dict_len);
+    KcemuDevice dev;
+    g_last = KcDecTimes();
+    return kc_sl_deflate(&dev, o, src, in_off, n, dst, dst_cap, out_off, g_last, counts);
+}
+uint64_t kcemu_flate_stateless_bound(uint64_t len, uint64_t dict_len) { return kc_sl_bound(len, dict_len); }
 
 // s2.ReadSeeker.ReadAt over m requests: kc_s2ranges_host.h's layout, Index.Find and sequence over plain memory.  Returns 0, -2 when
 // dst_cap is too small (nothing written), -1 for a request that names no input or wraps.

@@ -490,6 +490,37 @@ static kc_status begin_prescan(kc_ctx* c, const kc_zstd_opts* o, const Plan& pl,
     return KC_OK;
 }
 
+// the first-occurrence bits in front of the SpeedFastest HBM-table kernel, where zenc_first_filter says so.  The speculation re-run
+// reads the same bits (mp stays with the batch): they depend on the source alone, not on the parse.
+static kc_status begin_first(kc_ctx* c, const kc_zstd_opts* o, const Plan& pl, hipStream_t st, KcMatchParams& mp) {
+    if (c->cfg.zfast_first_filter == 0 && c->first_bits.p != nullptr) {  // switched off: the buffer (1/8 of the largest batch's source) goes back
+        (void)hipFree(c->first_bits.p);  // (no batch of this context is in flight: the last one's _end synchronised its stream)
+        c->first_bits.p = nullptr;
+        c->first_bits.cap = 0;
+    }
+    if (!zenc_first_filter(o, pl, c->cfg.zfast_first_filter != 0, c->job_hist != nullptr || c->job_primed, false)) return KC_OK;
+    if (zfast_use_lds(c, mp, pl.n_units, o->level)) return KC_OK;  // the LDS-table kernels have no table reads to save
+    // input that did not compress last time (the per-batch choice of the form for it): the pre-scan settles such units and the
+    // empty-group filter serves the rest; a pass over the whole source would cost more than the step it is meant to shorten
+    if (c->cfg.zfast_variant < 0 && c->last_incompressible) return KC_OK;
+    const size_t words = kc_zfast_first_words(mp.src, pl.rel_off[pl.n_units], pl.n_units);
+    // The bits are an accelerator, and the batch cutter's scratch budget does not count their buffer: a batch that fits without them
+    // must not fail for them.  Without room the batch runs as with the option off.
+    if (ensure(c, c->first_bits, words * 8) != KC_OK) {
+        c->oom = false;
+        c->err.clear();
+        return KC_OK;
+    }
+    KcFirstParams fp;
+    fp.src = mp.src;
+    fp.unit_off = mp.unit_off;
+    fp.n_units = pl.n_units;
+    fp.bits = (uint64_t*)c->first_bits.p;
+    kc_launch_zfast_first(fp, st);
+    mp.first_bits = fp.bits;
+    return KC_OK;
+}
+
 // the source is still arriving: per chunk, checksum + match finder + entropy stage + compaction on the chunk's stream behind its H2D copy
 static kc_status begin_feed(kc_ctx* c, const kc_zstd_opts* o, const Plan& pl, const uint8_t* d_src, uint8_t* d_dst, ChunkFeed* feed, hipStream_t st,
                             const KcMatchParams& mp, const KcEntropyParams& ep) {
@@ -554,6 +585,10 @@ kc_status batch_begin(kc_ctx* c, const kc_zstd_opts* o, const uint8_t* d_src_bas
     if ((s = begin_prescan(c, o, pl, fuse_xxh, st, mp, ep)) != KC_OK) return s;
     mp.unit_base = 0;
     ep.unit_base = 0;
+    // (a chunk-fed batch runs without the first-occurrence bits: its match finders start per chunk on streams of their own, and a
+    // pre-pass per chunk in front of each would sit on the path the feed exists to shorten — mp.first_bits stays null there)
+    if (feed == nullptr && (s = begin_first(c, o, pl, st, mp)) != KC_OK) return s;
+    c->last_first_bits = mp.first_bits != nullptr;
     if (feed == nullptr) {
         if (o->crc && !c->job_hist && !fuse_xxh) kc_launch_xxh64(d_src, (const uint64_t*)c->unit_off.p, n_units, (uint64_t*)c->xxh.p, st);  // (a job stream's checksum is the host's)
         HIPCHK(c, hipEventRecord(c->ev[1], st));

@@ -161,6 +161,7 @@ kc_status kc_ctx_set_option(kc_ctx* c, int key, int64_t v) {
         case KC_OPT_ZFAST_FILTER: g.zfast_filter = v != 0; break;
         case KC_OPT_ZFAST_VARIANT: if (v < -1 || v > 1) return KC_ERR_BAD_ARG; g.zfast_variant = v; break;
         case KC_OPT_ZFAST_PRESCAN: if (v < -1 || v > 1) return KC_ERR_BAD_ARG; g.zfast_prescan = v; break;
+        case KC_OPT_ZFAST_FIRST_FILTER: g.zfast_first_filter = v != 0; break;
         case KC_OPT_XXH_FIN_MODE: if (v < 0 || v > 3) return KC_ERR_BAD_ARG; g.xxh_fin_mode = v; break;
         case KC_OPT_JOB_PRIME: g.job_prime = v != 0; break;
         case KC_OPT_DSTREAM_BLOCKS: if (v < 1 || v > 4096) return KC_ERR_BAD_ARG; g.dstream_blocks = v; break;
@@ -206,6 +207,7 @@ int64_t kc_ctx_get_option(const kc_ctx* c, int key) {
         case KC_OPT_ZFAST_FILTER: return g.zfast_filter;
         case KC_OPT_ZFAST_VARIANT: return g.zfast_variant;
         case KC_OPT_ZFAST_PRESCAN: return g.zfast_prescan;
+        case KC_OPT_ZFAST_FIRST_FILTER: return g.zfast_first_filter;
         case KC_OPT_XXH_FIN_MODE: return g.xxh_fin_mode;
         case KC_OPT_JOB_PRIME: return g.job_prime;
         case KC_OPT_DSTREAM_BLOCKS: return g.dstream_blocks;
@@ -213,6 +215,7 @@ int64_t kc_ctx_get_option(const kc_ctx* c, int key) {
         case KC_OPT_STAGE2_STREAM: return (int64_t)(intptr_t)c->stream2;
         case KC_OPT_LAST_PATH: return c->last_path;
         case KC_OPT_LAST_PRESCAN_UNITS: return c->last_prescan_units;
+        case KC_OPT_LAST_FIRST_BITS: return c->last_first_bits;
         case KC_OPT_LAST_BATCHES: return c->last_batches;
         default: return -1;
     }
@@ -221,7 +224,7 @@ int64_t kc_ctx_get_option(const kc_ctx* c, int key) {
 static void ctx_free_scratch(kc_ctx* c) {
     DevBuf* bufs[] = {&c->unit_off, &c->unit_blk0, &c->stage_off, &c->seqs, &c->aux, &c->lits, &c->meta, &c->stage, &c->out_size, &c->xxh,
                       &c->redo, &c->popmask, &c->unit_list, &c->out_off, &c->blk_start, &c->unit_flags, &c->redo_blk, &c->pop_blk, &c->predef, &c->errflag, &c->tmp_src, &c->tmp_dst, &c->tables, &c->prof, &c->work, &c->work_off, &c->dictbuf, &c->proto, &c->dicthuf,
-                      &c->d_job_hist, &c->d_job_flags, &c->rawdef, &c->unit_raw, &c->unit_done, &c->probe_rel, &c->best_tables, &c->best_cur, &c->best_cost};
+                      &c->d_job_hist, &c->d_job_flags, &c->rawdef, &c->unit_raw, &c->unit_done, &c->probe_rel, &c->first_bits, &c->best_tables, &c->best_cur, &c->best_cost};
     for (DevBuf* b : bufs) {
         if (b->p) (void)hipFree(b->p);
         b->p = nullptr;

@@ -117,6 +117,8 @@ struct KcCfg {
     int64_t zfast_filter = 1;             // SpeedFastest HBM-table kernel: "nothing written there yet" filter in the idle sequence buffer (units without a sequence so far)
     int64_t xxh_fin_mode = 1;             // kc_xxh64_fin_kernel: how the payload of raw-only frames is stored (KcXxhFinParams.mode)
     int64_t zfast_prescan = -1;           // SpeedFastest: the no-match pre-scan (kc_zstd_prescan.hip): 0 off, 1 on, -1 when the previous batch did not compress
+    int64_t zfast_first_filter = 1;       // SpeedFastest HBM-table kernel: lookups at a unit's first position with a hash take "empty" without the table load
+                                          // (kc_zstd_first.hip; 22 k of 107 k DRAM reads per unit of text: profiles/zfast_first_filter_ab.txt)
     int64_t job_prime = 1;                // jobs of a WithConcurrentBlocks stream: tables primed from the overlap prefix on the device (0: on the host)
     int64_t dstream_blocks = 512;         // zstd stream reader: blocks per launch (1 .. 4096)
     int64_t s2_rstream_chunks = 4096;     // S2 stream reader: data chunks per launch (1 .. 4096; the sweep of profiles/s2_stream_reader.json)
@@ -182,8 +184,10 @@ struct kc_ctx {
     DevBuf unit_done, probe_rel;         // no-match pre-scan (kc_zstd_prescan.hip): per-unit verdicts; the probe positions of one block
     int probe_bs = 0;                    // block size probe_rel was built for
     uint32_t probe_n = 0;
+    DevBuf first_bits;                   // first-occurrence bits of the batch in flight (kc_zstd_first.hip), read by the SpeedFastest HBM-table kernel
     bool prescan_ran = false;            // the batch in flight ran the pre-scan (its verdicts are counted at the batch's end)
     int64_t last_prescan_units = 0;      // units of the last batch the pre-scan settled
+    int64_t last_first_bits = 0;         // the last zstd batch's match finder was handed first-occurrence bits (KC_OPT_LAST_FIRST_BITS)
     std::vector<uint32_t> job_redo_list;    // units of the speculation re-run in progress (their tables are re-primed)
     void* pend = nullptr;            // batch between kc_zstd_encode_units_dev_begin and _end (Pending)
     kc_ctx* chain_after = nullptr;   // pipelining: this context's match finder waits for that context's last one

@@ -44,6 +44,9 @@ struct KcMatchParams {
                                 // match and wrote the unit's block records: the match finder skips it
     int32_t xseg_k;             // SpeedFastest HBM kernel: a probe round continues across a skip-segment boundary once (s - nextEmit) >> 5
                                 // has reached this value (0: always; a large value: never, round 2's rounds)
+    const uint64_t* first_bits; // SpeedFastest HBM kernel, device or null: the first-occurrence bits of the launch's units (KcFirstParams.bits);
+                                // only where every unit's table starts empty and the unit has no history in front of it.  Null: every
+                                // lookup reads the table
 };
 // SpeedFastest: 8 lanes per unit, tables = n_launch x 2^15 x u32 in HBM, zeroed by the caller
 void kc_launch_zfast_match_grp(const KcMatchParams& P, uint32_t* tables, uint32_t n_launch, hipStream_t st);
@@ -158,6 +161,26 @@ struct KcPrescanParams {
 void kc_launch_zfast_prescan(const KcPrescanParams& P, hipStream_t st);
 // the probe positions of a block of `block_size` bytes relative to its start (host helper: fills rel[], returns the count)
 uint32_t kc_zfast_probe_positions(int block_size, uint32_t* rel, uint32_t cap);
+
+// ---- SpeedFastest first-occurrence bits (kc_zstd_first.hip) ----
+// One bit per source position p of a unit with p + 8 <= unit length: set only if no smaller position of the unit has the same
+// hash6(load64(p), ZF_TABLE_BITS).  The match finder's lookup at such a position finds a bucket that the unit has not written: in a
+// table that started empty the reference sees "no candidate" there whatever the parse did, and the lookup needs no load.  A set bit
+// is always a true first occurrence; the match finder needs no more than that (an unmarked position is looked up in the table).
+// The kernel marks every first occurrence; positions without 8 bytes behind them are never marked.
+// Layout: bit k of the 8-byte word w stands for the byte at (src rounded down to 16 bytes) + 64 * w + k, and the words of unit u are
+// stored u words further on — word (d >> 6) + u for a byte at distance d — so that units which share 64 source bytes share no word
+// (plain stores, no clearing).  kc_zfast_first_words gives the size.
+struct KcFirstParams {
+    const uint8_t* src;
+    const uint64_t* unit_off;   // device: n_units + 1
+    uint32_t n_units;
+    uint64_t* bits;             // out, device: kc_zfast_first_words(src, total bytes, n_units) words
+};
+void kc_launch_zfast_first(const KcFirstParams& P, hipStream_t st);
+static inline size_t kc_zfast_first_words(const void* src, uint64_t total_bytes, uint32_t n_units) {
+    return (size_t)((((uintptr_t)src & 15) + total_bytes + 63) >> 6) + n_units + 1;
+}
 
 // ---- job tables primed from the overlap prefix (kc_zstd_prime.hip) ----
 // encoder.ResetPrefix of a WithConcurrentBlocks job (enc_jobs.go:325-331 -> enc_fast.go:800-811, enc_dfast.go:1040-1050,

@@ -173,6 +173,13 @@ inline bool zenc_run_prescan(const kc_zstd_opts* o, const KcZencPlan& pl, int64_
     return want && o->level == KC_SPEED_FASTEST && fuse_xxh && !stream_mode && !o->all_lit_entropy && o->block_size >= 16 && pl.n_units > 0;
 }
 
+// The first-occurrence filter of the SpeedFastest HBM-table kernel (kc_zstd_first.hip): exactly where every unit's table starts
+// empty and the unit has nothing in front of it — no dictionary, no job prefix, no primed tables — and the whole batch is on the
+// device before the match finder starts (not chunk-fed).  The caller adds "the HBM-table kernel runs" (its own path choice).
+inline bool zenc_first_filter(const kc_zstd_opts* o, const KcZencPlan& pl, bool first_opt, bool jobs, bool fed) {
+    return first_opt && o->level == KC_SPEED_FASTEST && pl.hist0 == 0 && !jobs && !fed && pl.n_units > 0;
+}
+
 // ---- the parameter fill ----
 struct KcZencBufs {  // device pointers of the buffers a batch reserves
     const uint8_t* src = nullptr;        // what the kernels read: the source at the batch's first unit, or the work buffer (dictionary || unit)

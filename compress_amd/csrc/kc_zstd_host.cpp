@@ -218,6 +218,7 @@ kc_status kc_zstd_debug_parse_dev(kc_ctx* c, const kc_zstd_opts* o, const uint8_
     zenc_fill_params(&od, pl, b, cx, mp, ep);
     mp.src = d_src;
     if (o->dict != nullptr && o->dict_len > 0) { c->err = "debug parse does not take dictionaries"; return KC_ERR_UNSUPPORTED; }
+    c->last_first_bits = 0;  // (mp.first_bits stays null: the debug parse reads every bucket)
     if ((s = launch_match(c, mp, unit_off, n_units, n_units, bs, c->stream, o->level)) != KC_OK) return s;
     std::vector<KcBlkMeta> meta(nb);
     HIPCHK(c, hipMemcpyAsync(meta.data(), c->meta.p, (size_t)nb * sizeof(KcBlkMeta), hipMemcpyDeviceToHost, c->stream));

@@ -27,6 +27,10 @@
 //   * the repeat-offset candidate (known before the table lookup) and the offset-2 check after a match
 //     (enc_fast.go:250) are loaded in the same round trip as the table entries, the latter speculatively:
 //     the probes of the round are discarded when the offset-2 check hits (13 times per 128 KiB of text).
+//   * (kc_zfast_match_grp_kernel_first) a lookup at a position that is the first of its unit with its hash finds a bucket the
+//     unit has not written: where the tables start empty it takes "no candidate" without the load.  One bit per position says
+//     so (kc_zstd_first.hip computes them in front of the launch); the bits ride with the source bytes through the LDS window.
+//     107 k -> 85 k DRAM reads per 128 KiB of text, the writes unchanged (profiles/zfast_first_filter_ab.txt).
 // A probe round is thus: LDS window read -> {table, repeat, offset-2} loads -> candidate loads -> commit.
 // Output: per block, packed sequences (no literal bytes are copied here — the entropy kernel gathers
 // literals from the source using the sequence list) + a KcBlkMeta record.
@@ -41,6 +45,8 @@
 #endif
 #define ZW_MIRROR 32    // the first 32 ring bytes are mirrored behind the ring: 24-byte reads never wrap
 #define ZW_STRIDE (ZW_RB + ZW_MIRROR)
+#define ZW_BW 512       // ring bytes whose first-occurrence bits are kept: the newest ones (a refill starts below ZW_AHEAD bytes ahead of s and
+                        // adds 128: s and the probes behind it are never more than 448 bytes below the window's end)
 #define ZW_BK 4         // bytes in front of a probe / candidate position kept for the backward extension
 #ifndef ZW_AHEAD
 #define ZW_AHEAD 320    // refill while fewer than this many bytes are buffered ahead of s
@@ -51,18 +57,24 @@
 #define KC_TAB_ST(v, p) (*(p) = (v))
 
 
-template <int G, bool XSEG, bool FILT>
-__global__ __launch_bounds__(64) void kc_zfast_match_grp_kernel(KcMatchParams P, uint32_t* __restrict__ tables, uint32_t n_launch) {
+// FIRST: compiled with the first-occurrence bit window (kc_zfast_match_grp_kernel_first); without it nothing of the window exists
+template <int G, bool XSEG, bool FILT, bool FIRST>
+__device__ __forceinline__ void kc_zfast_match_grp_body(const KcMatchParams& P, uint32_t* __restrict__ tables, uint32_t n_launch) {
     constexpr int UPW = 64 / G;
     __shared__ __attribute__((aligned(16))) uint8_t ring_all[UPW * ZW_STRIDE];
-    __shared__ uint64_t sbuf_all[UPW * G];  // per unit: the last (nseq mod G) sequences, flushed G at a time as one 64-byte store
+    // LDS per wave decides how many waves a CU holds beside the entropy stage of the previous batch.  The sequence buffer (512 B) went
+    // into registers; the bit window (512 B) and the empty-group filter's words (512 B) exist only in the forms that use them.  Per
+    // wave, ring included: plain 8 448 B, plain + bits 8 960 (18 waves per CU, as before the bits), filter 8 960, filter + bits 9 472 (17).
+    __shared__ uint16_t bwin_all[FIRST ? UPW * (ZW_BW / 16) : 1];  // per unit: the first-occurrence bits (P.first_bits) of the newest ZW_BW ring bytes, one uint16 per 16-byte granule
+    __shared__ uint32_t fw_all[FILT ? UPW * 16 : 1];   // per unit: the 512 bits of the "nothing written there yet" filter
 #ifdef KC_MATCH_PRIO
     __builtin_amdgcn_s_setprio(KC_MATCH_PRIO);  // (measurement builds: the wave's issue priority beside a co-resident entropy kernel)
 #endif
     const int lane = (int)threadIdx.x;
     const int lig = lane % G, grp = lane / G;
     uint8_t* const ring = ring_all + grp * ZW_STRIDE;
-    uint64_t* const sbuf = sbuf_all + grp * G;
+    uint16_t* const bwin = bwin_all + (FIRST ? grp * (ZW_BW / 16) : 0);
+    uint64_t sreg = 0;  // lane i: the sequence number i (mod G) of the last (nseq mod G), flushed G at a time as one 64-byte store
     const uint32_t ui = blockIdx.x * UPW + (uint32_t)grp;
     const bool gact = ui < n_launch;
     const uint32_t u = gact ? (P.unit_list ? P.unit_list[ui] : P.unit_base + ui) : 0u;
@@ -97,16 +109,25 @@ __global__ __launch_bounds__(64) void kc_zfast_match_grp_kernel(KcMatchParams P,
     auto tagOf = [&](uint32_t v) -> uint32_t { return (TB > 0 ? (((v * 2654435761u) >> (32 - TB)) << EB) : 0u) | stamp; };
     const uint8_t* const srcLo = P.src;
     const uint8_t* const srcHi = P.src_end;
+    // First-occurrence bits (kc_zstd_first.hip): a set bit says that no smaller position of the unit hashes to the position's bucket, so
+    // this launch — whose tables start empty — has not written the bucket when the position is looked up: the entry is zero or carries a
+    // stale stamp, "no candidate" either way, and the lookup takes that result without the load.  The bits travel with the source bytes:
+    // a lane that refills 16 ring bytes loads the uint16 of the same granule.  fbits: the unit's row, indexed by the granule's distance
+    // from P.src rounded down to 16 bytes (every unit's words sit one 8-byte word behind the previous unit's: KcFirstParams).
+    const bool useB = FIRST && P.first_bits != nullptr;  // launch-uniform
+    const uint16_t* __restrict__ const fbits = useB ? (const uint16_t*)P.first_bits + 4 * (size_t)u : nullptr;
+    const uintptr_t forg = (uintptr_t)srcLo & ~(uintptr_t)15;
+    uint32_t rfb = 0;  // the bits that go with rf
 
-    // "Nothing written there yet" filter (round 3): until the unit emits its first sequence the 64 bytes of its sequence buffer are
-    // idle; they hold one bit per 64 consecutive buckets (4 table lines), set when the unit writes into them.  A lookup whose bit is
+    // "Nothing written there yet" filter (round 3): until the unit emits its first sequence, 64 bytes of LDS
+    // hold one bit per 64 consecutive buckets (4 table lines), set when the unit writes into them.  A lookup whose bit is
     // clear needs no load: the bucket is empty (zeroed, or stale-stamped) — on input without matches (high-entropy units: ~900
     // inserts into 2048 lines, no sequence ever) that is about half of the table reads, on a kernel bound by DRAM transactions.
     // Units whose tables arrive primed (dictionary, job prefix) do not use it; the first emit() ends it for good.
-    uint32_t* const fw = (uint32_t*)sbuf;
+    uint32_t* const fw = fw_all + (FILT ? grp * 16 : 0);
     bool useF = FILT && gact && P.empty_filter != 0 && P.hist0 == 0 && P.unit_hist == nullptr;
     if (FILT) {
-        sbuf[lig] = 0;  // (G == 8 lanes x 8 bytes: the whole buffer)
+        fw[2 * lig] = 0; fw[2 * lig + 1] = 0;  // (G == 8 lanes x 8 bytes: all of it)
         KC_EMU_SYNC();
     }
     int o1 = P.rep1, o2 = P.rep2;  // {1,4} (blockenc.go:78) or the dictionary's offsets (enc_base.go:189-195)
@@ -125,15 +146,13 @@ __global__ __launch_bounds__(64) void kc_zfast_match_grp_kernel(KcMatchParams P,
         int nextEmit = blkStart, s = blkStart;
         uint32_t firstLL = 0, firstOf = 0;
         auto emit = [&](int ll, int ml3, uint32_t of) {
-            if (FILT) useF = false;  // the buffer is the sequence buffer from here on
+            if (FILT) useF = false;  // (as when the filter's words were the sequence buffer's: the first sequence ends it)
             if (nseq == 0) { firstLL = (uint32_t)ll; firstOf = of; }
-            if (lig == 0) sbuf[nseq & (G - 1)] = seq_pack((uint32_t)ll, (uint32_t)ml3, of);
+            if (lig == (nseq & (G - 1))) sreg = seq_pack((uint32_t)ll, (uint32_t)ml3, of);  // (the arguments are group-uniform)
             nseq++;
             sumLL += ll;
             if ((nseq & (G - 1)) == 0) {  // group-uniform: G sequences buffered -> one coalesced store (8-byte scattered stores cost a DRAM write each)
-                __builtin_amdgcn_wave_barrier();
-                sq[nseq - G + lig] = sbuf[lig];
-                __builtin_amdgcn_wave_barrier();
+                sq[nseq - G + lig] = sreg;
             }
         };
         int SK = 5;  // kSearchStrength - 1
@@ -150,6 +169,7 @@ __global__ __launch_bounds__(64) void kc_zfast_match_grp_kernel(KcMatchParams P,
                 if (pend) {  // the refill issued one round ago has landed (its load precedes this round's loads in vmcnt order)
                     const int ro = (whi + 16 * lig) & (ZW_RB - 1);
                     *(uint4*)(ring + ro) = rf;
+                    if (useB) bwin[(ro & (ZW_BW - 1)) >> 4] = (uint16_t)rfb;
                     if (ro < ZW_MIRROR) *(uint4*)(ring + ZW_RB + ro) = rf;
                     whi += 16 * G;
                     if (whi - wlo > ZW_RB) wlo = whi - ZW_RB;
@@ -166,6 +186,7 @@ __global__ __launch_bounds__(64) void kc_zfast_match_grp_kernel(KcMatchParams P,
                     const uint8_t* q = abase + whi + 16 * lig;
                     rf = make_uint4(0, 0, 0, 0);
                     if (q < srcHi) rf = *(const uint4*)q;  // aligned: never leaves the 16-byte granule of a readable byte
+                    if (useB) rfb = q < srcHi ? fbits[((uintptr_t)q - forg) >> 4] : 0u;
                     pend = true;
                 }
                 // ---------------- probe positions of this round ----------------
@@ -194,10 +215,16 @@ __global__ __launch_bounds__(64) void kc_zfast_match_grp_kernel(KcMatchParams P,
                 }
                 // R = the 20 source bytes [p-4, p+16): D1:D2 = cv, the rest feeds the fused candidate compares
                 uint32_t D0 = 0, D1 = 0, D2 = 0, D3 = 0, D4 = 0;
+                bool first0 = false, first1 = false;  // p / p + 1 is the first position of the unit with its hash: the bucket is empty
                 if (valid) {
                     const int a = p + boff - ZW_BK;
                     const int a4 = a & ~3;
                     if (a4 >= wlo && a4 + 24 <= whi) {
+                        const int b0 = a + ZW_BK, b1 = b0 + 1;  // (p and p + 1 lie in the window with the bytes)
+                        if (useB && whi - b0 <= ZW_BW) {  // ... and among its newest ZW_BW bytes; elsewhere a position counts as "not first"
+                            first0 = ((bwin[(b0 & (ZW_BW - 1)) >> 4] >> (b0 & 15)) & 1u) != 0;
+                            first1 = ((bwin[(b1 & (ZW_BW - 1)) >> 4] >> (b1 & 15)) & 1u) != 0;
+                        }
                         const uint32_t* r = (const uint32_t*)(ring + (a4 & (ZW_RB - 1)));
                         const uint32_t r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3], r4 = r[4], r5 = r[5];
                         const uint32_t sh = (uint32_t)(a & 3);
@@ -225,11 +252,11 @@ __global__ __launch_bounds__(64) void kc_zfast_match_grp_kernel(KcMatchParams P,
                     h1 = hash6(cv >> 8, ZF_TABLE_BITS);
                     if (FILT && useF) {  // group-uniform
                         const uint32_t g0 = h0 >> 6, g1 = h1 >> 6;
-                        if ((fw[g0 >> 5] >> (g0 & 31u)) & 1u) c0 = KC_TAB_LD(&tab[h0]);
-                        if ((fw[g1 >> 5] >> (g1 & 31u)) & 1u) c1 = KC_TAB_LD(&tab[h1]);
+                        if (!first0 && ((fw[g0 >> 5] >> (g0 & 31u)) & 1u)) c0 = KC_TAB_LD(&tab[h0]);
+                        if (!first1 && ((fw[g1 >> 5] >> (g1 & 31u)) & 1u)) c1 = KC_TAB_LD(&tab[h1]);
                     } else {
-                        c0 = KC_TAB_LD(&tab[h0]);
-                        c1 = KC_TAB_LD(&tab[h1]);
+                        if (!first0) c0 = KC_TAB_LD(&tab[h0]);
+                        if (!first1) c1 = KC_TAB_LD(&tab[h1]);
                     }
                 }
                 const int repIndex = p - o1 + 2;
@@ -445,7 +472,7 @@ __global__ __launch_bounds__(64) void kc_zfast_match_grp_kernel(KcMatchParams P,
         }
         pend = false;  // a refill still in flight at the end of a block is dropped; the window itself stays valid
         __builtin_amdgcn_wave_barrier();
-        if (lig < (nseq & (G - 1))) sq[(nseq & ~(G - 1)) + lig] = sbuf[lig];  // the buffered tail of the sequence list
+        if (lig < (nseq & (G - 1))) sq[(nseq & ~(G - 1)) + lig] = sreg;  // the buffered tail of the sequence list
         const int extra = nextEmit < blkEnd ? blkEnd - nextEmit : 0;
         const int nlit = sumLL + extra;
         const bool rle = nseq == 1 && nlit <= 1 && (int)firstLL == nlit && firstOf - 3u == 1u;
@@ -469,9 +496,25 @@ __global__ __launch_bounds__(64) void kc_zfast_match_grp_kernel(KcMatchParams P,
     }
 }
 
+template <int G, bool XSEG, bool FILT>
+__global__ __launch_bounds__(64) void kc_zfast_match_grp_kernel(KcMatchParams P, uint32_t* __restrict__ tables, uint32_t n_launch) {
+    kc_zfast_match_grp_body<G, XSEG, FILT, false>(P, tables, n_launch);
+}
+template <int G, bool XSEG, bool FILT>
+__global__ __launch_bounds__(64) void kc_zfast_match_grp_kernel_first(KcMatchParams P, uint32_t* __restrict__ tables, uint32_t n_launch) {
+    kc_zfast_match_grp_body<G, XSEG, FILT, true>(P, tables, n_launch);
+}
+
 void kc_launch_zfast_match_grp(const KcMatchParams& P, uint32_t* tables, uint32_t n_launch, hipStream_t st) {
     // Two compiled forms, the same bytes: the plain one (rounds inside one skip segment, no filter) is ~1 % faster on compressible
     // input, where neither addition ever acts; the other one is for input that yields no matches (P.tuned: the host's choice).
-    if (P.tuned) hipLaunchKernelGGL((kc_zfast_match_grp_kernel<8, true, true>), dim3((n_launch + 7) / 8), dim3(64), 0, st, P, tables, n_launch);
-    else hipLaunchKernelGGL((kc_zfast_match_grp_kernel<8, false, false>), dim3((n_launch + 7) / 8), dim3(64), 0, st, P, tables, n_launch);
+    // Each of them with and without the first-occurrence bits (P.first_bits).
+    const dim3 grid((n_launch + 7) / 8), block(64);
+    if (P.first_bits != nullptr) {
+        if (P.tuned) hipLaunchKernelGGL((kc_zfast_match_grp_kernel_first<8, true, true>), grid, block, 0, st, P, tables, n_launch);
+        else hipLaunchKernelGGL((kc_zfast_match_grp_kernel_first<8, false, false>), grid, block, 0, st, P, tables, n_launch);
+    } else {
+        if (P.tuned) hipLaunchKernelGGL((kc_zfast_match_grp_kernel<8, true, true>), grid, block, 0, st, P, tables, n_launch);
+        else hipLaunchKernelGGL((kc_zfast_match_grp_kernel<8, false, false>), grid, block, 0, st, P, tables, n_launch);
+    }
 }

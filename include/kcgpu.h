@@ -208,7 +208,9 @@ typedef enum {
     KC_OPT_S2_HOOK_HOST_FIRST = 35,  /* KC_S2_HOOK_HOST_FIRST     kc_s2_encode_block: how many callers at a time are left to the host's built-in encoder (they get -1) before the overflow goes to the device: -1 (default) the host's hardware threads, 0 every caller to the device (see kc_s2_encode_block) */
     KC_OPT_DSTREAM_BLOCKS = 36,      /* (no variable)             zstd stream reader (kc_zstd_dstream_new): blocks per launch, 1 .. 4096 (default 512); at 1 every block is a launch of its own */
     KC_OPT_S2_RSTREAM_CHUNKS = 37,   /* (no variable)             S2 stream reader (kc_s2_rstream_new): data chunks per launch, 1 .. 4096 (default 4096: the smallest value within the spread of the best rate at 64 KiB blocks, profiles/s2_stream_reader.json); at 1 every chunk is a launch of its own */
+    KC_OPT_ZFAST_FIRST_FILTER = 38,  /* KC_ZFAST_FIRST_FILTER     SpeedFastest HBM-table kernel, batches whose tables start empty (no dictionary, no job prefix, not chunk-fed): 1 (default) = a streaming pre-pass marks every position that is the first of its unit with its table hash, and the match finder takes "no candidate" there without reading the table; 0 = every lookup reads the table.  The frames are the same bytes either way (profiles/zfast_first_filter_ab.txt has the measurements) */
     KC_OPT_LAST_PRESCAN_UNITS = 102, /* read-only: units of the last batch the pre-scan settled */
+    KC_OPT_LAST_FIRST_BITS = 103,    /* read-only: 1 = the last zstd batch's match finder was handed first-occurrence bits (KC_OPT_ZFAST_FIRST_FILTER), 0 = it read every bucket */
     KC_OPT_LAST_PATH = 100,          /* read-only: KC_PATH_HBM / KC_PATH_LDS the last batch ran on */
     KC_OPT_LAST_BATCHES = 101        /* read-only: device batches the last kc_zstd_encode_units_dev / kc_s2_encode_*_dev call was cut into */
 } kc_option;

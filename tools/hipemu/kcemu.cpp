@@ -8,6 +8,7 @@
 #include "../../compress_amd/csrc/kc_misc.hip"
 #include "../../compress_amd/csrc/kc_zstd_entropy.hip"
 #include "../../compress_amd/csrc/kc_zstd_prescan.hip"
+#include "../../compress_amd/csrc/kc_zstd_first.hip"
 #include "../../compress_amd/csrc/kc_zstd_prime.hip"
 #include "../../compress_amd/csrc/kc_zstd_match_dfast.hip"
 #include "../../compress_amd/csrc/kc_zstd_match_better.hip"
@@ -42,6 +43,8 @@
 // it is one outside a heap block), filled with 0xA7 when it is made; copies are memcpy; the kernels run on the emulator.
 static uint64_t g_budget = 0;   // kcemu_set_scratch_budget: what the batch decoders may ask for (0: anything)
 static KcDecTimes g_last;       // what the last batch decoder's sequence reported
+static int g_first_opt = 1;     // kcemu_set_first_filter: KC_OPT_ZFAST_FIRST_FILTER as kcemu_zstd_batch sees it (the library's default: on)
+static int g_first_used = 0;    // the last kcemu_zstd_batch gave its match finder first-occurrence bits
 struct KcemuDevice : KcDecDevice {
     std::vector<void*> buf;
     std::vector<size_t> cap;
@@ -378,9 +381,9 @@ int kcemu_zfast_parse(const uint8_t* src, const uint64_t* unit_off, uint32_t n, 
 
 // the SpeedFastest HBM-table group kernel (kc_zfast_match_grp_kernel<8>) over n units; tables: n x 2^15 u32 kept by the caller between
 // calls (epoch 0: zeroed by the caller; else the launch's stamp)
-int kcemu_zfast_parse_grp(const uint8_t* src, const uint64_t* unit_off, uint32_t n, int block_size, int window, int stream_mode, uint64_t* seqs,
-                          KcBlkMeta* meta, uint32_t seq_stride, const uint32_t* unit_blk0, int spec_w0, int spec_grow, int pos_bits, uint32_t* tables,
-                          uint32_t epoch, int xseg_k) {
+static int kcemu_zfast_grp(const uint8_t* src, const uint64_t* unit_off, uint32_t n, int block_size, int window, int stream_mode, uint64_t* seqs,
+                           KcBlkMeta* meta, uint32_t seq_stride, const uint32_t* unit_blk0, int spec_w0, int spec_grow, int pos_bits, uint32_t* tables,
+                           uint32_t epoch, int xseg_k, const uint64_t* first_bits) {
     KcMatchParams P;
     memset(&P, 0, sizeof(P));
     P.src = src;
@@ -402,10 +405,49 @@ int kcemu_zfast_parse_grp(const uint8_t* src, const uint64_t* unit_off, uint32_t
     P.xseg_k = xseg_k & 0xFFFFFF;
     P.tuned = P.xseg_k < (1 << 20) ? 1 : 0;  // (2^20: the plain form, rounds inside one skip segment, no filter)
     P.empty_filter = (xseg_k >> 24) & 1 ? 0 : 1;  // (bit 24 of the argument switches the filter off)
+    P.first_bits = first_bits;
     hipemu::set_group(8);  // 8 units per wave, the groups diverge freely
     kc_launch_zfast_match_grp(P, tables, n, nullptr);
     hipemu::set_group(64);
     return 0;
+}
+int kcemu_zfast_parse_grp(const uint8_t* src, const uint64_t* unit_off, uint32_t n, int block_size, int window, int stream_mode, uint64_t* seqs,
+                          KcBlkMeta* meta, uint32_t seq_stride, const uint32_t* unit_blk0, int spec_w0, int spec_grow, int pos_bits, uint32_t* tables,
+                          uint32_t epoch, int xseg_k) {
+    return kcemu_zfast_grp(src, unit_off, n, block_size, window, stream_mode, seqs, meta, seq_stride, unit_blk0, spec_w0, spec_grow, pos_bits, tables, epoch,
+                           xseg_k, nullptr);
+}
+// the same with the first-occurrence bits of kcemu_zfast_first over the same src / unit_off (the tables must start empty for this launch)
+int kcemu_zfast_parse_grp_first(const uint8_t* src, const uint64_t* unit_off, uint32_t n, int block_size, int window, int stream_mode, uint64_t* seqs,
+                                KcBlkMeta* meta, uint32_t seq_stride, const uint32_t* unit_blk0, int spec_w0, int spec_grow, int pos_bits, uint32_t* tables,
+                                uint32_t epoch, int xseg_k, const uint64_t* first_bits) {
+    return kcemu_zfast_grp(src, unit_off, n, block_size, window, stream_mode, seqs, meta, seq_stride, unit_blk0, spec_w0, spec_grow, pos_bits, tables, epoch,
+                           xseg_k, first_bits);
+}
+
+// kc_zfast_first_kernel over n units: bits = kcemu_zfast_first_words(src, unit_off[n] - unit_off[0], n) words (KcFirstParams has the layout)
+uint64_t kcemu_zfast_first_words(const uint8_t* src, uint64_t total_bytes, uint32_t n) { return kc_zfast_first_words(src, total_bytes, n); }
+int kcemu_zfast_first(const uint8_t* src, const uint64_t* unit_off, uint32_t n, uint64_t* bits) {
+    KcFirstParams P;
+    P.src = src;
+    P.unit_off = unit_off;
+    P.n_units = n;
+    P.bits = bits;
+    kc_launch_zfast_first(P, nullptr);
+    return 0;
+}
+// KC_OPT_ZFAST_FIRST_FILTER for kcemu_zstd_batch (default 1), and whether its last call handed the match finder the bits
+void kcemu_set_first_filter(int on) { g_first_opt = on; }
+int kcemu_last_first_filter() { return g_first_used; }
+// kc_zenc_host.h's rule for a batch of n units at `level` with hist0 bytes of dictionary content, as the jobs of a stream, chunk-fed
+int kcemu_zenc_first_filter(int level, int hist0, int jobs, int fed, uint32_t n, int first_opt) {
+    kc_zstd_opts o;
+    kc_zstd_opts_default(&o);
+    kc_zstd_opts_level(&o, level);
+    kci::KcZencPlan pl;
+    pl.hist0 = hist0;
+    pl.n_units = n;
+    return kci::zenc_first_filter(&o, pl, first_opt != 0, jobs != 0, fed != 0) ? 1 : 0;
 }
 
 // kc_xxh64_fin_kernel: the checksum field of every frame, and the payload of the frames flagged in unit_raw copied from the source
@@ -511,6 +553,17 @@ int kcemu_zstd_batch(const uint8_t* src, const uint64_t* unit_off, uint32_t n, i
         hipemu::set_group(64);
     }
     // the match finder over n_launch units (all, or the re-run's list), in the forced form
+    // the first-occurrence bits under the library's rule (the speculation re-run below reads the same ones)
+    std::vector<uint64_t> first_bits;
+    g_first_used = 0;
+    if (use_grp && zenc_first_filter(&o, pl, g_first_opt != 0, false, false)) {
+        first_bits.assign(kc_zfast_first_words(M.src, pl.rel_off[n], n), 0xA7A7A7A7A7A7A7A7ull);
+        KcFirstParams F;
+        F.src = M.src; F.unit_off = M.unit_off; F.n_units = n; F.bits = first_bits.data();
+        kc_launch_zfast_first(F, nullptr);
+        M.first_bits = first_bits.data();
+        g_first_used = 1;
+    }
     std::vector<uint64_t> btab;
     uint32_t bcur[2] = {0, 0};
     int32_t bcost[96];

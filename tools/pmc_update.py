@@ -48,11 +48,13 @@ def main():
                         per[r[ik][:60]][r[idp]] += float(r[iv])
                 res[ctr] = {k: v[max(v)] * 1024.0 for k, v in per.items() if k.startswith(("kc_", "void kc_"))}  # the last dispatch of each kernel = the timed step
                 shutil.rmtree(d, ignore_errors=True)
-            # the first warm-up step runs without the pre-scan (its plain-form match finder is left out); FETCH_SIZE doubled for the two
+            # the first warm-up step runs without the pre-scan: its plain-form match finder, with or without the first-occurrence bits,
+            # and the pre-pass of those bits (kc_zstd_first.hip) run in no later step and are left out; FETCH_SIZE doubled for the two
             # kernels that stream 16 bytes per lane (MI355X_MICROARCH.md: gfx950 tallies such reads at half their bytes — the checksum
             # kernel calibrates it: it reads exactly 4 GiB and the counter says 2.149e9), raw for everything else
             for ctr in res:
-                res[ctr] = {k: v for k, v in res[ctr].items() if "kc_zfast_match_grp_kernel<8, false" not in k}
+                res[ctr] = {k: v for k, v in res[ctr].items() if "kc_zfast_match_grp_kernel<8, false" not in k and "kc_zfast_match_grp_kernel_first<8, false" not in k
+                            and "kc_zfast_first_kernel" not in k}
             tot = int(sum(sum(v.values()) for v in res.values()) + sum(v for k, v in res.get("FETCH_SIZE", {}).items() if "kc_xxh64_fin_kernel" in k or "kc_compact_kernel" in k))
             if len(res) == 2 and tot > 0:
                 algo = 32768 * 131072 * 2 + 32768 * 13

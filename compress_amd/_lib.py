@@ -63,6 +63,8 @@ SYMBOLS = [
     "kc_flate_inflate_dev", "kc_flate_inflate", "kc_flate_inflate_bound_dev", "kc_flate_inflate_bound",
     "kc_gzip_inflate_dev", "kc_gzip_inflate", "kc_gzip_inflate_bound_dev", "kc_gzip_inflate_bound",
     "kc_zlib_inflate_dev", "kc_zlib_inflate", "kc_zlib_inflate_bound_dev", "kc_zlib_inflate_bound",
+    "kc_zip_dir_load", "kc_zip_dir_free", "kc_zip_dir_count", "kc_zip_dir_base_offset", "kc_zip_dir_comment", "kc_zip_dir_entry", "kc_zip_dir_members",
+    "kc_zip_read_dev", "kc_zip_read", "kc_zip_read_bound",
     "kc_flate_wopts_default", "kc_flate_wopts_free", "kc_flate_wopts_level", "kc_flate_wopts_end", "kc_flate_wopts_block",
     "kc_flate_deflate_bound", "kc_flate_deflate_dev", "kc_flate_deflate", "kc_gzip_deflate_dev", "kc_gzip_deflate",
     "kc_flate_swopts_default", "kc_flate_swopts_free", "kc_flate_swopts_eof", "kc_flate_swopts_dict", "kc_flate_stateless_bound",
@@ -110,6 +112,41 @@ def declare_s2_index(L):
     L.kc_s2_index_entries.restype = C.c_uint32
     L.kc_s2_index_stream.argtypes = [vp, u64, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.kc_s2_index_stream.restype = C.c_int
+
+
+class ZipEntry(C.Structure):
+    """kc_zip_entry (include/kcgpu.h): zip.FileHeader's directory fields; name, comment and extra point into the archive buffer."""
+    _fields_ = [("name", C.c_void_p), ("comment", C.c_void_p), ("extra", C.c_void_p), ("name_len", C.c_uint32), ("comment_len", C.c_uint32),
+                ("extra_len", C.c_uint32), ("non_utf8", C.c_uint32), ("creator_version", C.c_uint16), ("reader_version", C.c_uint16),
+                ("flags", C.c_uint16), ("method", C.c_uint16), ("modified_time", C.c_uint16), ("modified_date", C.c_uint16), ("crc32", C.c_uint32),
+                ("compressed_size64", C.c_uint64), ("uncompressed_size64", C.c_uint64), ("header_offset", C.c_int64),
+                ("external_attrs", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ZipMember(C.Structure):
+    """kc_zip_member (include/kcgpu.h): one row of the member table of kc_zip_read."""
+    _fields_ = [("header_offset", C.c_int64), ("compressed_size", C.c_uint64), ("uncompressed_size", C.c_uint64), ("crc32", C.c_uint32),
+                ("method", C.c_uint16), ("flags", C.c_uint16), ("is_dir", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def declare_zip_dir(L):
+    """ctypes signatures of the kc_zip_dir_* functions (plain host code: any library that exports them)."""
+    vp, u64 = C.c_void_p, C.c_uint64
+    L.kc_zip_dir_load.argtypes = [vp, u64, C.POINTER(vp)]
+    L.kc_zip_dir_load.restype = C.c_int
+    L.kc_zip_dir_free.argtypes = [vp]
+    L.kc_zip_dir_free.restype = None
+    L.kc_zip_dir_count.argtypes = [vp]
+    L.kc_zip_dir_count.restype = u64
+    L.kc_zip_dir_base_offset.argtypes = [vp]
+    L.kc_zip_dir_base_offset.restype = C.c_int64
+    L.kc_zip_dir_comment.argtypes = [vp, C.POINTER(C.c_uint32)]
+    L.kc_zip_dir_comment.restype = vp
+    L.kc_zip_dir_entry.argtypes = [vp, u64, C.POINTER(ZipEntry)]
+    L.kc_zip_dir_entry.restype = C.c_int
+    L.kc_zip_dir_members.argtypes = [vp, u64, u64, vp]
+    L.kc_zip_dir_members.restype = C.c_int
+    return L
 
 
 def lib_path():
@@ -298,6 +335,13 @@ def load():
         f = getattr(L, n)
         f.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, vp]
         f.restype = C.c_int
+    declare_zip_dir(L)
+    for n in ("kc_zip_read_dev", "kc_zip_read"):
+        f = getattr(L, n)
+        f.argtypes = [vp, vp, u64, vp, C.c_uint32, vp, u64, vp, vp]
+        f.restype = C.c_int
+    L.kc_zip_read_bound.argtypes = [vp, vp, u64, vp, C.c_uint32, vp, vp]
+    L.kc_zip_read_bound.restype = C.c_int
     L.kc_flate_wopts_default.argtypes = []
     L.kc_flate_wopts_default.restype = vp
     L.kc_flate_wopts_free.argtypes = [vp]

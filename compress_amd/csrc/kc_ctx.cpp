@@ -243,6 +243,7 @@ static void ctx_free_scratch(kc_ctx* c) {
     free_all(c->fl, sizeof(c->fl) / sizeof(DevBuf));    // flate / gzip readers (kc_flate_api.cpp)
     free_all(c->df, sizeof(c->df) / sizeof(DevBuf));    // flate / gzip writers (kc_deflate_api.cpp)
     free_all(c->sl, sizeof(c->sl) / sizeof(DevBuf));    // flate / gzip stateless writers (kc_stateless_api.cpp)
+    free_all(c->zp, sizeof(c->zp) / sizeof(DevBuf));    // zip members (kc_zip_api.cpp)
     // what the context remembered about the freed buffers' contents
     c->predef_ready = false;
     c->tab_owner = 0;

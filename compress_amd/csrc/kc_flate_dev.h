@@ -28,6 +28,7 @@
 #define KCFL_SIZE 5u
 #define KCFL_DICTIONARY 6u
 #define KCFL_RAW_EOF 100u  // internal: the raw io.EOF of inflate_gen.go:114-122, 142-151, 210-219 — ReadAll ends without an error
+#define KCFL_OVER 101u     // internal: the next bytes would pass the room the caller gave (O.cap, or KCFL_MAX_OUT without writing): fl_over()
 #define KCFL_MAX_OUT ((uint64_t)1 << 30)  // decoded bytes per input this library serves
 
 struct KcFlateParams {
@@ -263,9 +264,16 @@ __device__ __forceinline__ void fl_flush(FlOut& O, const int lane) {
     O.nlit = 0;
 }
 
-// One DEFLATE stream from B on.  KCFL_OK: the final block ended (or the raw io.EOF of the reference's extra-bit reads: what was
-// decoded stands); the bit reader is left where the reference's is.
+// what KCFL_OVER is to the flate, gzip and zlib passes: the write pass was planned by the sizing pass, so bytes beyond the plan are a
+// broken stream; the sizing pass met the library's limit
 template <bool WRITE>
+__device__ __forceinline__ uint32_t fl_over(const uint32_t e) { return e == KCFL_OVER ? (WRITE ? KCFL_CORRUPT : KCFL_SIZE) : e; }
+
+// One DEFLATE stream from B on.  KCFL_OK: the final block ended (or the raw io.EOF of the reference's extra-bit reads: what was
+// decoded stands); the bit reader is left where the reference's is.  KCFL_OVER: the room ended; nothing is written beyond it.
+// AVAIL_FIRST (zip): a stored block that the input's end cuts short is KCFL_OVER where the bytes it HAS pass the room -- the
+// reference hands those out before it reports the short read (copyData, inflate.go:634-670) -- and its bytes count towards O.d.
+template <bool WRITE, bool AVAIL_FIRST = false>
 __device__ __forceinline__ uint32_t fl_inflate(FlBits& B, FlOut& O, FlLds& L, const int lane) {
     const FlTab TL = {L.prim_l, L.sym_l, L.cnt[0], L.aux[0]}, TD = {L.prim_d, L.sym_d, L.cnt[1], L.aux[1]}, TC = {L.prim_c, L.sym_c, L.cnt[2], L.aux[2]};
     const FlTab TF = {L.prim_f, L.sym_f, L.cnt[3], L.aux[3]};
@@ -285,8 +293,15 @@ __device__ __forceinline__ uint32_t fl_inflate(FlBits& B, FlOut& O, FlLds& L, co
             const uint32_t w = uniu(ld32(B.src + p));
             const uint32_t len = w & 0xFFFFu;
             if ((w >> 16) != (len ^ 0xFFFFu)) { fl_seek(B, p + 4); return KCFL_CORRUPT; }
-            if (B.end - (p + 4) < len) { fl_seek(B, B.end); return KCFL_EOF; }
-            if (len > limit - O.d) return WRITE ? KCFL_CORRUPT : KCFL_SIZE;
+            if (B.end - (p + 4) < len) {
+                if (AVAIL_FIRST) {
+                    if (B.end - (p + 4) > limit - O.d) return KCFL_OVER;
+                    O.d += B.end - (p + 4);  // (handed out by the reference; a failed input's range is zero-filled, so not copied)
+                }
+                fl_seek(B, B.end);
+                return KCFL_EOF;
+            }
+            if (len > limit - O.d) return KCFL_OVER;
             if (WRITE) {
                 fl_flush<WRITE>(O, lane);
                 uint8_t* o = O.dst + O.d;
@@ -369,7 +384,7 @@ __device__ __forceinline__ uint32_t fl_inflate(FlBits& B, FlOut& O, FlLds& L, co
             uint32_t e = fl_sym<KCFL_PB_L>(B, TB, CB, max_read, &v);
             if (e) return e;
             if (v < 256) {
-                if (O.d >= limit) return WRITE ? KCFL_CORRUPT : KCFL_SIZE;
+                if (O.d >= limit) return KCFL_OVER;
                 if (WRITE) {
                     if ((uint32_t)lane == O.nlit) O.lit = v;
                     O.nlit++;
@@ -407,7 +422,7 @@ __device__ __forceinline__ uint32_t fl_inflate(FlBits& B, FlOut& O, FlLds& L, co
             } else return KCFL_CORRUPT;
             const uint64_t mine = O.d - O.base;  // bytes of this stream so far
             if ((uint64_t)dist > mine + O.hist_len) return KCFL_CORRUPT;  // dist > dict.histSize()
-            if (length > limit - O.d) return WRITE ? KCFL_CORRUPT : KCFL_SIZE;
+            if (length > limit - O.d) return KCFL_OVER;
             if (WRITE) {
                 fl_flush<WRITE>(O, lane);
                 KC_WAVE_SYNC();  // what other lanes wrote so far is read back from here on
@@ -438,7 +453,7 @@ __device__ __forceinline__ uint32_t fl_input(const KcFlateParams& P, const uint6
     *size = 0; *used = 0; *n_members = 0;
     if (!P.gzip) {
         fl_seek(B, begin);
-        uint32_t e = fl_inflate<WRITE>(B, O, L, lane);
+        uint32_t e = fl_over<WRITE>(fl_inflate<WRITE>(B, O, L, lane));
         if (e == KCFL_RAW_EOF) e = KCFL_OK;
         fl_flush<WRITE>(O, lane);
         if (e) return e;
@@ -492,7 +507,7 @@ __device__ __forceinline__ uint32_t fl_input(const KcFlateParams& P, const uint6
         if (flg >> 5) return KCFL_HEADER;
         fl_seek(B, p);
         O.base = O.d;
-        uint32_t e = fl_inflate<WRITE>(B, O, L, lane);
+        uint32_t e = fl_over<WRITE>(fl_inflate<WRITE>(B, O, L, lane));
         fl_flush<WRITE>(O, lane);
         if (e == KCFL_RAW_EOF) e = KCFL_OK;  // the member "ends": the trailer read below then finds nothing
         if (e) return e;
@@ -597,7 +612,7 @@ __device__ __forceinline__ uint32_t fl_zlib_input(const KcFlateParams& P, const 
     FlOut O;
     O.dst = dst; O.cap = cap; O.d = 0; O.hist = P.dict; O.hist_len = have_dict ? P.dict_len : 0; O.base = 0; O.nlit = 0; O.lit = 0;
     fl_seek(B, p);
-    uint32_t e = fl_inflate<WRITE>(B, O, L, lane);
+    uint32_t e = fl_over<WRITE>(fl_inflate<WRITE>(B, O, L, lane));
     fl_flush<WRITE>(O, lane);
     if (e == KCFL_RAW_EOF) e = KCFL_OK;  // the stream "ends" at the input's end: the trailer read below then finds nothing
     if (e) return e;

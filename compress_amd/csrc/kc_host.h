@@ -181,6 +181,7 @@ struct kc_ctx {
     DevBuf fl[8];                        // flate / gzip inflate (FL_*, kc_flate_host.h): offsets, the sizing pass's results, the write pass's verdicts, the dictionary
     DevBuf df[8];                        // flate / gzip HuffmanOnly writers (DF_*, kc_deflate_host.h): offsets, the block records, sizes, CRCs, the edge words
     DevBuf sl[13];                       // flate / gzip stateless writers (SL_*, kc_stateless_host.h): offsets, the block records, the tokens, sizes, CRCs, the dictionary
+    DevBuf zp[13];                       // zip members (ZP_*, kc_zip_host.h): the member table, the locate kernel's results, the plan, chunk CRCs, verdicts
     DevBuf unit_done, probe_rel;         // no-match pre-scan (kc_zstd_prescan.hip): per-unit verdicts; the probe positions of one block
     int probe_bs = 0;                    // block size probe_rel was built for
     uint32_t probe_n = 0;

@@ -712,6 +712,89 @@ kc_status kc_zlib_inflate_bound_dev(kc_ctx* ctx, const kc_flate_ropts* o, const 
 kc_status kc_zlib_inflate_bound(kc_ctx* ctx, const kc_flate_ropts* o, const uint8_t* src, const uint64_t* in_off, uint32_t n,
                                 uint64_t* bound, uint32_t* status, uint64_t* consumed);
 
+/* ---- zip.NewReader / File.Open over a batch of archive members (zip/reader.go, zip/struct.go) ----
+ * Two halves.  The DIRECTORY is read on the host, from an archive held in memory, without a device or a context: kc_zip_dir_load is
+ * Reader.init (reader.go:146-207) with readDirectoryEnd (:605-682: the end record searched in the last 1 KiB, then the last 65 KiB;
+ * the zip64 locator and end record followed; baseOffset, and a valid header at offset 0 winning over it, :668-679), and
+ * readDirectoryHeader (:386-564) until a bad header, the count compared modulo 65536 only (:188).  The zip64 extra replaces only the
+ * fields that are maxed out, a short one is KC_ZIP_FORMAT, an uncompressed size of 2^32 - 1 stands without one (:446-561); NonUTF8
+ * follows the three-way rule of :428-444.  Returns KC_ZIP_OK and *dir, or the class of the reference's error and *dir = null:
+ * KC_ZIP_FORMAT (zip.ErrFormat), KC_ZIP_EOF (io.ErrUnexpectedEOF; also the plain io.EOF that the ReaderAt returns for a zip64 end
+ * record past the archive's end and that a directory running exactly to the archive's end yields), KC_ZIP_COMMENT ("zip: invalid
+ * comment length").  The entries' name, comment and extra and the archive comment point into buf, which must outlive the object.
+ * header_offset has baseOffset applied.  kc_zip_dir_members fills the member table below from the entries [first, first + n).
+ *
+ * The MEMBERS are read on the device, one call over one source buffer and a table of n members whose header offsets are absolute in
+ * that buffer (the entries of several archives laid into one buffer are one batch).  Every member gets the verdict of f.Open(),
+ * io.ReadAll, Close (reader.go:247-362, 368-381, 566-603), in this order:
+ *   1. thirty bytes at header_offset: not all inside the buffer, or a negative offset: KC_ZIP_READAT (the ReaderAt's own error, io.EOF
+ *      over a byte slice); a wrong signature: KC_ZIP_FORMAT.  The body starts 30 + name length + extra length of the LOCAL header on.
+ *   2. is_dir (a name ending in "/"): a nonzero uncompressed size is KC_ZIP_FORMAT, else the member is empty and KC_ZIP_OK (:252-267).
+ *   3. a method other than 0 (Store) and 8 (Deflate): KC_ZIP_ALGORITHM (:270-273).
+ *   4. a compressed or uncompressed size above 1 GiB: KC_ZIP_SIZE, a limit of this library and its one deviation from the reference.
+ *   5. the body is [body, body + compressed_size) clipped to the buffer (a SectionReader over a shorter file ends early).  With d the
+ *      bytes the decompressor yields before it ends or fails (the bytes of a cut stored DEFLATE block included): d above the
+ *      uncompressed size is KC_ZIP_FORMAT whatever follows (:331-333); else the decompressor's own KC_FL_CORRUPT / KC_FL_EOF stands;
+ *      else d below the uncompressed size is KC_FL_EOF (:338-340).  The raw io.EOF of kc_flate_inflate counts as an end.
+ *   6. flag bit 3: the data descriptor behind body + compressed_size, 16 bytes with the signature 0x08074b50 and 12 without (:566-603);
+ *      absent or short: KC_FL_EOF; its CRC field, then the CRC-32 of the decoded bytes, against the table's: KC_ZIP_CHECKSUM.
+ *   7. else the CRC-32 of the decoded bytes is compared where the table's is nonzero (:352-357): KC_ZIP_CHECKSUM.
+ * The device decodes every member ONCE, straight to its place, bounded by the size the table states: there is no sizing pass.
+ * out_off[n + 1] is the prefix sum of the stated uncompressed sizes over the members that get a range.  None get: the verdicts of
+ * rules 1 to 4; a stored member whose clipped compressed size differs from its uncompressed size; a deflated member whose stated
+ * size exceeds 1032 x its clipped compressed size + 1032 (DEFLATE cannot expand further: it is walked without writing to learn
+ * whether it is KC_FL_CORRUPT or KC_FL_EOF).  KC_ERR_DST_TOO_SMALL when out_off[n] > dst_cap: the layout is filled, nothing is
+ * written.  A member that fails with a range keeps it, zero-filled.  CRC-32s are computed on the device: wave-wide for a deflated
+ * member, per 64 KiB chunk with the chunk values combined for a stored one.
+ * kc_zip_read: host buffers, staged whole as kc_flate_inflate stages a group (KC_ERR_UNSUPPORTED when the archive and the layout
+ * exceed the scratch budget); kc_zip_read_bound: the layout and the verdicts that need no decoding (rules 1 to 4 and the size
+ * rules above; the others KC_ZIP_OK). */
+enum {
+    KC_ZIP_OK = 0,          /* per member: also KC_FL_CORRUPT (1) and KC_FL_EOF (2) */
+    KC_ZIP_FORMAT = 16,     /* zip.ErrFormat "zip: not a valid zip file" */
+    KC_ZIP_EOF = 17,        /* directory only: io.ErrUnexpectedEOF / io.EOF */
+    KC_ZIP_COMMENT = 18,    /* directory only: "zip: invalid comment length" */
+    KC_ZIP_ALGORITHM = 19,  /* zip.ErrAlgorithm "zip: unsupported compression algorithm" */
+    KC_ZIP_CHECKSUM = 20,   /* zip.ErrChecksum "zip: checksum error" */
+    KC_ZIP_READAT = 21,     /* the ReaderAt's error for the local header: io.EOF, or "negative offset" */
+    KC_ZIP_SIZE = 22        /* a member above 1 GiB: this library's limit */
+};
+typedef struct kc_zip_entry {   /* zip.FileHeader, the fields read from the directory (struct.go:86-160) */
+    const uint8_t* name;        /* Name, Comment, Extra: raw bytes inside the archive buffer */
+    const uint8_t* comment;
+    const uint8_t* extra;
+    uint32_t name_len, comment_len, extra_len;
+    uint32_t non_utf8;          /* NonUTF8 */
+    uint16_t creator_version, reader_version, flags, method, modified_time, modified_date;
+    uint32_t crc32;
+    uint64_t compressed_size64, uncompressed_size64;
+    int64_t header_offset;      /* File.headerOffset: baseOffset applied */
+    uint32_t external_attrs;
+    uint32_t reserved;
+} kc_zip_entry;
+typedef struct kc_zip_member {
+    int64_t header_offset;      /* absolute in the source buffer */
+    uint64_t compressed_size, uncompressed_size;
+    uint32_t crc32;
+    uint16_t method, flags;
+    uint32_t is_dir;            /* the name ends in "/" */
+    uint32_t reserved;
+} kc_zip_member;
+typedef struct kc_zip_dir kc_zip_dir;
+int kc_zip_dir_load(const uint8_t* buf, uint64_t len, kc_zip_dir** dir);
+void kc_zip_dir_free(kc_zip_dir* dir);
+uint64_t kc_zip_dir_count(const kc_zip_dir* dir);
+int64_t kc_zip_dir_base_offset(const kc_zip_dir* dir);
+const uint8_t* kc_zip_dir_comment(const kc_zip_dir* dir, uint32_t* len);
+int kc_zip_dir_entry(const kc_zip_dir* dir, uint64_t i, kc_zip_entry* out);
+int kc_zip_dir_members(const kc_zip_dir* dir, uint64_t first, uint64_t n, kc_zip_member* out);
+kc_status kc_zip_read_dev(kc_ctx* ctx, const uint8_t* d_src, uint64_t src_len, const kc_zip_member* members, uint32_t n, uint8_t* d_dst,
+                          uint64_t dst_cap, uint64_t* out_off, uint32_t* status);
+kc_status kc_zip_read(kc_ctx* ctx, const uint8_t* src, uint64_t src_len, const kc_zip_member* members, uint32_t n, uint8_t* dst,
+                      uint64_t dst_cap, uint64_t* out_off, uint32_t* status);
+kc_status kc_zip_read_bound(kc_ctx* ctx, const uint8_t* src, uint64_t src_len, const kc_zip_member* members, uint32_t n, uint64_t* out_off,
+                            uint32_t* status);
+
 /* ---- flate.NewWriter / gzip.NewWriterLevel at flate.HuffmanOnly over a batch of independent inputs (deflate) ----
  * The output of every input is, byte for byte, what flate.NewWriter(w, flate.HuffmanOnly); Write(input); Close() writes
  * (flate/deflate.go:755-770 write, :701-708 storeHuff, :865-880 close; flate/huffman_bit_writer.go:987-1174 writeBlockHuff,

@@ -30,12 +30,15 @@
 #include "../../compress_amd/csrc/kc_flate_inflate.hip"
 #include "../../compress_amd/csrc/kc_flate_deflate.hip"
 #include "../../compress_amd/csrc/kc_flate_stateless.hip"
+#include "../../compress_amd/csrc/kc_zip.hip"
+#include "../../compress_amd/csrc/kc_zip_dir.cpp"    // (host code: zip.NewReader's directory pass, exported from this library as from the product)
 
 #include "../../compress_amd/csrc/kc_s2dec_host.h"
 #include "../../compress_amd/csrc/kc_s2ranges_host.h"
 #include "../../compress_amd/csrc/kc_flate_host.h"
 #include "../../compress_amd/csrc/kc_deflate_host.h"
 #include "../../compress_amd/csrc/kc_stateless_host.h"
+#include "../../compress_amd/csrc/kc_zip_host.h"
 #include "../../compress_amd/csrc/kc_zstd_opts.cpp"  // (host code: the encoder's option functions)
 #include "../../compress_amd/csrc/kc_zenc_host.h"    // (host code: the rules of the zstd encode batch)
 
@@ -235,6 +238,15 @@ int kcemu_zlib_inflate(const uint8_t* src, const uint64_t* in_off, uint32_t n, c
     if (dict_len > 32768) { dict += dict_len - 32768; dict_len = 32768; }
     o.dict = dict; o.dict_len = dict_len;
     return kcemu_flate(o, src, in_off, n, dst, dst_cap, out_off, bound, status, consumed);
+}
+
+// n x (f.Open(); io.ReadAll; Close) over the members of one source buffer: kc_zip_host.h's sequence over plain memory.  dst null:
+// the layout and the verdicts that need no decoding.  Returns 0, -2 when dst_cap is too small (out_off holds the layout, nothing is written).
+int kcemu_zip_read(const uint8_t* src, uint64_t src_len, const kc_zip_member* members, uint32_t n, uint8_t* dst, uint64_t dst_cap, uint64_t* out_off,
+                   uint32_t* status) {
+    KcemuDevice dev;
+    g_last = KcDecTimes();
+    return kc_zp_read(&dev, src, src_len, members, n, dst, dst_cap, out_off, status, dst == nullptr, g_last);
 }
 
 // N x (flate.NewWriter(w, HuffmanOnly); Write(input); Close() -- or Flush() with end = 1): kc_deflate_host.h's sequence over plain

@@ -199,7 +199,9 @@ __device__ __forceinline__ float sl_shannon_term(const uint32_t v, const float i
 #pragma clang fp contract(off)
     const float n = (float)v;
     float b = -sl_fast_log2(n * inv);
-    if (b < 1.0f) b = 1.0f;  // atLeastOne
+    // atLeastOne (huffman_code.go:374-382) also clamps at 15.  Not restated: EstimatedBits is only asked where a block goes to
+    // writeBlockDynamic, i.e. with at most 30 720 tokens (15/16 of 32 767) and an EOB, so n * inv >= 1 / 30 721 and b <= 14.91.
+    if (b < 1.0f) b = 1.0f;
     const float p = b * n;
     return p;
 }

@@ -691,5 +691,158 @@ long long goref_gunzip(const uint8_t* src, long long n, int multistream, uint8_t
         return -1;
     }
 }
+}  // extern "C"
+// ---- the write side of flate and gzip (portable flavour): StatelessDeflate / NewStatelessWriter, NewWriter(w, HuffmanOnly), a bare
+// huffmanBitWriter, gzip.NewWriterLevel — the judge of tests/deflate_model.py and tests/stateless_model.py.  All return the number of
+// bytes the writer's io.Writer received, -1 after a panic, -2 where out is too small, -5 where the reference returned an error.
+namespace {
+struct FlateSink : io::WriterImpl {  // bytes.Buffer
+    go::Slice<go::byte> buf;
+    std::tuple<go::Int, go::error> Write(go::Slice<go::byte> p) override { buf = go::append_all(buf, p); return std::tuple<go::Int, go::error>(go::len(p), go::error()); }
+};
+go::Slice<go::byte> flate_bytes(const uint8_t* p, long long n) {  // (nil for a null pointer, an empty non-nil slice for n == 0)
+    if (p == nullptr) return go::Slice<go::byte>();
+    go::Slice<go::byte> s = go::make_slice<go::byte>(n);
+    if (n) memcpy((void*)s.p, p, (size_t)n);
+    return s;
+}
+long long flate_result(const FlateSink& sink, uint8_t* out, long long cap) {
+    if (sink.buf.n > cap) return -2;
+    if (sink.buf.n) memcpy(out, sink.buf.p, (size_t)sink.buf.n);
+    return sink.buf.n;
+}
+// Write / Flush / Close in the order of `ops`: an op >= 0 is Write(data[pos:op]) (pos: the end of the Write before), -1 Flush(), -2 Close()
+template <class W> bool flate_run_ops(W* w, const go::Slice<go::byte>& data, const long long* ops, long long n_ops) {
+    long long pos = 0;
+    for (long long i = 0; i < n_ops; i++) {
+        go::error e;
+        if (ops[i] >= 0) {
+            if (ops[i] < pos || ops[i] > data.n) go::panic_str("driver: a Write that does not follow the one before");
+            e = std::get<1>(w->Write(data.sl(pos, ops[i])));
+            pos = ops[i];
+        } else if (ops[i] == -1) e = w->Flush();
+        else e = w->Close();
+        if (e != go::nil) return false;
+    }
+    return true;
+}
+}  // namespace
+extern "C" {
+// flate.StatelessDeflate(w, in, eof, dict); dict may be null (nil)
+long long goref_flate_stateless(const uint8_t* in, long long n, int eof, const uint8_t* dict, long long dict_len, uint8_t* out, long long cap) {
+    using namespace go;
+    rt::Scope scope;
+    try {
+        flate_init();
+        FlateSink sink;
+        error e = flate::StatelessDeflate(io::Writer(&sink), flate_bytes(in, n), eof != 0, dict_len > 0 ? flate_bytes(dict, dict_len) : Slice<byte>());
+        if (e != nil) return -5;
+        return flate_result(sink, out, cap);
+    } catch (const go::Panic&) { return -1; }
+}
+// w := flate.NewStatelessWriter(dst); one Write(data[prev:cut]) per cut; Close()
+long long goref_flate_stateless_writer(const uint8_t* data, long long n, const long long* cuts, long long n_cuts, uint8_t* out, long long cap) {
+    using namespace go;
+    rt::Scope scope;
+    try {
+        flate_init();
+        FlateSink sink;
+        Slice<byte> src = flate_bytes(data ? data : (const uint8_t*)"", n);
+        auto* w = flate::NewStatelessWriter(io::Writer(&sink));
+        long long pos = 0;
+        for (long long i = 0; i < n_cuts; i++) {
+            if (cuts[i] < pos || cuts[i] > n) panic_str("driver: cuts must ascend");
+            if (std::get<1>(w->Write(src.sl(pos, cuts[i]))) != nil) return -5;
+            pos = cuts[i];
+        }
+        if (w->Close() != nil) return -5;
+        return flate_result(sink, out, cap);
+    } catch (const go::Panic&) { return -1; }
+}
+// w, _ := flate.NewWriter(dst, flate.HuffmanOnly), then the ops (see flate_run_ops)
+long long goref_flate_huffman_only(const uint8_t* data, long long n, const long long* ops, long long n_ops, uint8_t* out, long long cap) {
+    using namespace go;
+    rt::Scope scope;
+    try {
+        flate_init();
+        FlateSink sink;
+        Slice<byte> src = flate_bytes(data ? data : (const uint8_t*)"", n);
+        auto r = flate::NewWriter(io::Writer(&sink), Int(flate::HuffmanOnly));
+        if (std::get<1>(r) != nil) return -5;
+        if (!flate_run_ops(std::get<0>(r), src, ops, n_ops)) return -5;
+        return flate_result(sink, out, cap);
+    } catch (const go::Panic&) { return -1; }
+}
+// A bare newHuffmanBitWriter(dst) with logNewTablePenalty = penalty, driven as compressor.write / storeHuff drive theirs with a window
+// of `block` bytes: writeBlockHuff(false, chunk, false) for every full block that more input follows, writeBlockHuff(false, rest, true)
+// for the rest; then end 0: writeStoredHeader(0, true) + flush (close), 1: writeStoredHeader(0, false) + flush (syncFlush), 2: flush
+// alone (what the reference's own test of writeBlockHuff does behind its single block)
+long long goref_flate_block_huff(const uint8_t* data, long long n, long long block, int penalty, int end, uint8_t* out, long long cap) {
+    using namespace go;
+    rt::Scope scope;
+    try {
+        flate_init();
+        FlateSink sink;
+        Slice<byte> src = flate_bytes(data ? data : (const uint8_t*)"", n);
+        flate::huffmanBitWriter* w = flate::newHuffmanBitWriter(io::Writer(&sink));
+        w->logNewTablePenalty = Uint(K((long long)penalty));
+        long long pos = 0;
+        while (n - pos > block) { w->writeBlockHuff(false, src.sl(pos, pos + block), false); pos += block; }
+        if (n - pos > 0) w->writeBlockHuff(false, src.sl(pos, n), true);
+        if (end == 0) w->writeStoredHeader(Int(K(0LL)), true);
+        else if (end == 1) w->writeStoredHeader(Int(K(0LL)), false);
+        w->flush();
+        if (w->err != nil) return -5;
+        return flate_result(sink, out, cap);
+    } catch (const go::Panic&) { return -1; }
+}
+// tokens := indexTokens(toks); a fresh newHuffmanBitWriter(dst).writeBlockDynamic(&tokens, false, input, sync); flush — the reference's own
+// TestWriteBlockDynamic / ...Sync (huffman_bit_writer_test.go writeToType); input null: nil.  A token is the reference's word: a literal, or
+// matchType | (length - 3) << 22 | (offset - 1)
+long long goref_flate_block_dynamic(const uint32_t* toks, long long n_toks, const uint8_t* input, long long n, int sync, uint8_t* out, long long cap) {
+    using namespace go;
+    rt::Scope scope;
+    try {
+        flate_init();
+        FlateSink sink;
+        Slice<flate::token> in = make_slice<flate::token>(n_toks);
+        for (long long i = 0; i < n_toks; i++) in.p[i] = flate::token(uint32::raw(toks[i]));
+        auto* t = new (rt::tag) flate::tokens_T();
+        t->indexTokens(in);
+        flate::huffmanBitWriter* w = flate::newHuffmanBitWriter(io::Writer(&sink));
+        w->writeBlockDynamic(t, false, flate_bytes(input, n), sync != 0);
+        w->flush();
+        if (w->err != nil) return -5;
+        return flate_result(sink, out, cap);
+    } catch (const go::Panic&) { return -1; }
+}
+// t := indexTokens(toks); t.EstimatedBits() (-1: a panic)
+long long goref_flate_estimated_bits(const uint32_t* toks, long long n_toks) {
+    using namespace go;
+    rt::Scope scope;
+    try {
+        flate_init();
+        Slice<flate::token> in = make_slice<flate::token>(n_toks);
+        for (long long i = 0; i < n_toks; i++) in.p[i] = flate::token(uint32::raw(toks[i]));
+        auto* t = new (rt::tag) flate::tokens_T();
+        t->indexTokens(in);
+        return t->EstimatedBits().v;
+    } catch (const go::Panic&) { return -1; }
+}
+// z, _ := gzip.NewWriterLevel(dst, level) for level -2 (HuffmanOnly) or -3 (StatelessCompression), then the ops (see flate_run_ops)
+long long goref_gzip_write(int level, const uint8_t* data, long long n, const long long* ops, long long n_ops, uint8_t* out, long long cap) {
+    using namespace go;
+    rt::Scope scope;
+    try {
+        flate_init();
+        if (level != -2 && level != -3) return -4;
+        FlateSink sink;
+        Slice<byte> src = flate_bytes(data ? data : (const uint8_t*)"", n);
+        auto r = gzip::NewWriterLevel(io::Writer(&sink), Int(K((long long)level)));
+        if (std::get<1>(r) != nil) return -5;
+        if (!flate_run_ops(std::get<0>(r), src, ops, n_ops)) return -5;
+        return flate_result(sink, out, cap);
+    } catch (const go::Panic&) { return -1; }
+}
 #endif
 }

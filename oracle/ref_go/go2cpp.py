@@ -347,6 +347,8 @@ class Emitter:
             ty = fun[1]
         elif fun[0] == "paren" and fun[1][0] == "typeexpr":
             ty = fun[1][1]
+        elif fun[0] == "paren" and fun[1][0] == "ident" and self.is_type_name(fun[1][1]):  # (T)(x)
+            ty = ("name", None, fun[1][1])
         elif fun[0] == "paren" and fun[1][0] == "unary" and fun[1][1] == "*":  # (*T)(x)
             inner = fun[1][2]
             if inner[0] == "ident" and self.is_type_name(inner[1]):
@@ -531,17 +533,16 @@ class Emitter:
                 ct = "Array<%s, %d>" % (self.ctype(et), mx)
             else:
                 ct = self.ctype(ty)
-            pos = None
+            base, step = None, 0  # the index is `base + step` (a literal key, or none, plus the elements since): written as one constant
             for k, val in elems:
                 if k is not None:
-                    pos = self.ex(k)
-                    idx = pos
-                    nxt = "(%s + K(1LL))" % pos
+                    base, step = self.ex(k), 0
+                if base is None:
+                    idx = "K(%dLL)" % step
                 else:
-                    idx = pos if pos is not None else "K(0LL)"
-                    nxt = "(%s + K(1LL))" % idx
+                    idx = base if step == 0 else "(%s + K(%dLL))" % (base, step)
                 lines.append("%s[%s] = %s;" % (v, idx, self.elem_val(et, val)))
-                pos = nxt
+                step += 1
         elif u[0] == "slice":
             et = u[1]
             ct = self.ctype(ty)
@@ -969,10 +970,10 @@ class Emitter:
         val = lhs[1] if len(lhs) > 1 else None
         if key is not None and key != ("ident", "_"):
             if define:
-                self.w("Int %s = Int::raw(%s);" % (mangle(key[1]), i))
+                self.w("auto %s = go::rangekey(%s, %s);" % (mangle(key[1]), r, i))
                 self.declare(key[1])
             else:
-                self.w("%s = Int::raw(%s);" % (self.ex(key), i))
+                self.w("%s = go::rangekey(%s, %s);" % (self.ex(key), r, i))
         if val is not None and val != ("ident", "_"):
             if define:
                 self.w("auto %s = go::rangeval(%s, %s);" % (mangle(val[1]), r, i))

@@ -133,6 +133,39 @@ struct K {
 };
 constexpr long long cn(K k) { return (long long)k.v; }  // array lengths and the like
 
+// ---- float32 ----
+// Go's float32 as a type of its own: every operation rounds to single precision, and an untyped constant beside a float32 IS a
+// float32 (C++'s `1.0 / f` would compute in double).  No implicit way out of the type: float64(f) and int(f) are conversions.
+struct float32 {
+    float v;
+    float32() = default;
+    constexpr float32(K k) : v((float)(double)k) {}
+    explicit constexpr float32(double d) : v((float)d) {}
+    static constexpr float32 raw(float x) { float32 r{}; r.v = x; return r; }
+    constexpr float32 operator-() const { return raw(-v); }
+    constexpr float32 operator+() const { return *this; }
+};
+// float32 with float32, or with an untyped constant (a double or a K here) on either side; both operands are deduced, so that these
+// never take part in the overload resolution of other types
+template <class A, class B> struct f32_pair : std::integral_constant<bool,
+    (std::is_same<A, float32>::value && (std::is_same<B, float32>::value || std::is_same<B, double>::value || std::is_same<B, K>::value)) ||
+    (std::is_same<B, float32>::value && (std::is_same<A, double>::value || std::is_same<A, K>::value))> {};
+constexpr float f32_of(float32 f) { return f.v; }
+constexpr float f32_of(double d) { return (float)d; }
+constexpr float f32_of(K k) { return (float)(double)k; }
+#define GORT_F32_ARITH(OP) \
+    template <class A, class B, class = typename std::enable_if<f32_pair<A, B>::value>::type> \
+    constexpr float32 operator OP(A a, B b) { return float32::raw(f32_of(a) OP f32_of(b)); } \
+    template <class B, class = typename std::enable_if<f32_pair<float32, B>::value>::type> \
+    inline float32& operator OP##=(float32& a, B b) { a = a OP b; return a; }
+GORT_F32_ARITH(+) GORT_F32_ARITH(-) GORT_F32_ARITH(*) GORT_F32_ARITH(/)
+#undef GORT_F32_ARITH
+#define GORT_F32_CMP(OP) \
+    template <class A, class B, class = typename std::enable_if<f32_pair<A, B>::value>::type> \
+    constexpr bool operator OP(A a, B b) { return f32_of(a) OP f32_of(b); }
+GORT_F32_CMP(==) GORT_F32_CMP(!=) GORT_F32_CMP(<) GORT_F32_CMP(<=) GORT_F32_CMP(>) GORT_F32_CMP(>=)
+#undef GORT_F32_CMP
+
 // ---- typed integers ----
 template <class T> struct I {
     typedef T raw_type;
@@ -144,6 +177,7 @@ template <class T> struct I {
     template <class U> explicit constexpr I(I<U> o) : v((T)o.v) {}
     explicit constexpr I(double d) : v((T)d) {}
     explicit constexpr I(float d) : v((T)d) {}
+    explicit constexpr I(float32 f) : v((T)f.v) {}
     static constexpr I raw(T x) { I r{}; r.v = x; return r; }
     constexpr I* operator->() { return this; }
     friend constexpr I operator+(I a, I b) { return raw((T)((UT)a.v + (UT)b.v)); }
@@ -202,7 +236,6 @@ typedef I<uint64_t> uintptr;
 typedef I<uint8_t> byte;
 typedef I<int32_t> rune;
 typedef double float64;
-typedef float float32;
 
 template <class T> struct is_goint : std::false_type {};
 template <class T> struct is_goint<I<T>> : std::true_type {};
@@ -213,6 +246,7 @@ constexpr long long idx(T i) { return (long long)i.v; }
 inline double f64(K k) { return (double)k.v; }
 template <class T> double f64(I<T> i) { return (double)i.v; }
 inline double f64(double d) { return d; }
+inline double f64(float32 f) { return (double)f.v; }
 
 // x := <expr>: an untyped constant becomes int (float64), everything else keeps its type (by value)
 inline Int def(K k) { return Int(k); }
@@ -543,6 +577,8 @@ inline double Sqrt(double x) { return sqrt(x); }
 inline double Abs(double x) { return fabs(x); }
 inline double Float64frombits(go::uint64 b) { double d; memcpy(&d, &b.v, 8); return d; }
 inline go::uint64 Float64bits(double d) { uint64_t b; memcpy(&b, &d, 8); return go::uint64::raw(b); }
+inline go::float32 Float32frombits(go::uint32 b) { float f; memcpy(&f, &b.v, 4); return go::float32::raw(f); }
+inline go::uint32 Float32bits(go::float32 f) { uint32_t b; memcpy(&b, &f.v, 4); return go::uint32::raw(b); }
 }  // namespace math
 namespace cpuinfo {  // internal/cpuinfo: what the amd64 flavour's dispatch helpers ask (the driver can force the non-BMI2 routines)
 inline int& force() { static int f = -1; return f; }  // -1: the host's CPU; 0: pretend BMI1/BMI2 are absent
@@ -653,6 +689,7 @@ template <class X> uint64 Load64(const Slice<byte>& b, X i) { return binary::Lit
 inline void Store16(const Slice<byte>& b, uint16 v) { binary::LittleEndian.PutUint16(b, v); }
 inline void Store32(const Slice<byte>& b, uint32 v) { binary::LittleEndian.PutUint32(b, v); }
 inline void Store64(const Slice<byte>& b, uint64 v) { binary::LittleEndian.PutUint64(b, v); }
+template <class X> void Store64(const Slice<byte>& b, X i, uint64 v) { binary::LittleEndian.PutUint64(go::slice(b, go::idx(i), -1), v); }
 }  // namespace le
 
 namespace go {
@@ -666,4 +703,9 @@ inline long long rangelen(K n) { return (long long)n.v; }
 template <class T> T rangeval(const Slice<T>& s, long long i) { return s.p[i]; }
 template <class T, long long N> T rangeval(const Array<T, N>& s, long long i) { return s.a[i]; }
 template <class T, long long N> T rangeval(Array<T, N>* const& s, long long i) { return s->a[i]; }
+// (a string ranges over runes: ASCII only here, the translation has no UTF-8 decoder)
+inline rune rangeval(const String& s, long long i) { if ((unsigned char)s.s[(size_t)i] >= 0x80) panic_str("range over a non-ASCII string: not translated"); return rune::raw((unsigned char)s.s[(size_t)i]); }
+// the key of `for i := range x`: int, except over an integer, where it has that integer's type
+template <class X> Int rangekey(const X&, long long i) { return Int::raw(i); }
+template <class T> I<T> rangekey(const I<T>&, long long i) { return I<T>::raw((T)i); }
 }  // namespace go

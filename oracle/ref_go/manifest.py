@@ -1,6 +1,8 @@
 """What go2cpp.py translates: the reference's Go files of the zstd encode path, per package in dependency order; declarations
 left out (decoder halves, goroutine variants, String() methods of debug output) and the few source patches, each with its reason.
-Also the inflate side of flate and gzip's reader (portable flavour only): what io.ReadAll over flate.NewReaderDict / gzip.NewReader runs."""
+Also the inflate side of flate and gzip's reader (portable flavour only): what io.ReadAll over flate.NewReaderDict / gzip.NewReader runs;
+and the two DEFLATE writers that have no match finder state: flate.StatelessDeflate / NewStatelessWriter, flate.NewWriter(w, HuffmanOnly)
+and gzip.NewWriterLevel at those two levels (huffman_bit_writer.go, huffman_code.go, token.go, stateless.go whole; the rest by name)."""
 
 CFG = {
     "packages": [
@@ -15,8 +17,12 @@ CFG = {
                   "zstd/blockdec.go", "zstd/framedec.go", "zstd/fse_decoder.go",
                   "zstd/fse_decoder_generic.go", "zstd/encoder_options.go", "zstd/enc_jobs.go", "zstd/encoder.go", "zstd/decoder_options.go", "zstd/decoder.go"]),
         # the inflate side of flate and gzip's reader: the judge of tests/flate_model.py (regmask_other.go: the shift masks of a non-amd64 build, all ones)
-        ("flate", ["flate/regmask_other.go", "flate/dict_decoder.go", "flate/inflate.go", "flate/inflate_gen.go"]),
-        ("gzip", ["gzip/gunzip.go"]),
+        # ... and the write side: the bit writer with both block writers, the Huffman code builder and its two sorts, the token
+        # histograms with EstimatedBits, the stateless encoder (matchlen_generic.go: its matchLen), the HuffmanOnly compressor
+        ("flate", ["flate/regmask_other.go", "flate/dict_decoder.go", "flate/inflate.go", "flate/inflate_gen.go",
+                   "flate/fast_encoder.go", "flate/token.go", "flate/huffman_code.go", "flate/huffman_sortByFreq.go", "flate/huffman_sortByLiteral.go",
+                   "flate/huffman_bit_writer.go", "flate/matchlen_generic.go", "flate/stateless.go", "flate/deflate.go"]),
+        ("gzip", ["gzip/gunzip.go", "gzip/gzip.go"]),
     ],
     # path -> names of top-level declarations (or Type.method) that are not translated
     "skip": {
@@ -38,6 +44,7 @@ CFG = {
                              "WithResumeFrom", "decompressor.ResetCP", "decompressor.applyCP", "decompressor.WriteTo"},
         "flate/dict_decoder.go": {"dictDecoder.appendWindow"},                        # only the checkpoint callback reads the window
         "gzip/gunzip.go": {"crcer", "crcUpdater", "Reader.WriteTo", "Reader.Close", "le"},   # WriteTo and its digest plumbing; ReadAll goes through Read
+        "flate/token.go": {"tokens.VarInt", "tokens.FromVarInt"},                     # a test aid (bytes.Reader, binary.ReadUvarint)
     },
     # path -> the ONLY declarations taken from that file (the rest of it is the decoder / the streaming writer)
     "only": {
@@ -64,6 +71,15 @@ CFG = {
                             "Encoder.closeJobs", "Encoder.ReadFrom", "Encoder.readFromJobs"},
         # of the five copies of the block body, generated per concrete reader type, the generic one (the driver's reader is a flate.Reader)
         "flate/inflate_gen.go": {"decompressor.huffmanGenericReader", "decompressor.huffmanBlockDecoder"},
+        # the constants and loads that token.go, huffman_bit_writer.go and stateless.go use (not the level 1-6 encoders' shared state)
+        "flate/fast_encoder.go": {"baseMatchOffset", "baseMatchLength", "maxMatchOffset", "load3232", "load6432"},
+        # what flate.NewWriter(w, HuffmanOnly) runs: no match finder, no level 1-9 
+        "flate/deflate.go": {"NoCompression", "BestSpeed", "BestCompression", "DefaultCompression", "HuffmanOnly", "ConstantCompression", "maxMatchLength",
+                             "maxStoreBlockSize", "debugDeflate", "compressionLevel", "compressor", "compressor.init", "compressor.reset", "compressor.fillBlock", "compressor.storeHuff",
+                             "compressor.write", "compressor.syncFlush", "compressor.close", "NewWriter", "Writer", "Writer.Write", "Writer.Flush", "Writer.Close",
+                             "Writer.Reset"},
+        # the Writer and the header it writes (the Header type itself comes from gunzip.go)
+        "gzip/gzip.go": {"BestSpeed", "BestCompression", "StatelessCompression", "Writer", "Writer.*", "NewWriterLevel"},
         # constants and the block / literals type enumerations the encoder shares with the decoder
         # initPredefined builds the predefined DECODER tables first and copies their normalised counts into the encoders
     },
@@ -76,6 +92,7 @@ CFG = {
         "zstd.jobState": {"jobCh", "resultCh", "cond", "workerWg", "flusherWg", "inputPool", "outputPool", "overlapPool"},
         "flate.decompressor": {"cb", "cp", "hasCP", "uncOffset", "cpBuf"},   # the checkpoint callback and resume state
         "gzip.Reader": {"br"},                                              # the bufio.Reader of a source without ReadByte
+        "flate.compressor": {"h", "tokens", "fast", "state"},               # what levels 1-9 keep: queued tokens, the fast encoders, the hash chains
 },
     # path -> [(regular expression, replacement, why)]: source patches applied before parsing
     "patches": {
@@ -159,8 +176,6 @@ CFG = {
             (r'\t"bufio"\n\t"compress/flate"\n', '\t"errors"\n', "no bufio branch; compress/flate only lent its error types"),
             (r"type CorruptInputError = flate\.CorruptInputError\n", 'var errCorrupt = errors.New("flate: corrupt input")\nvar errInternal = errors.New("flate: internal error")\n',
              "the two error classes as values"),
-            (r"\tdebugDecode = false\n", "\tdebugDecode = false\n\n\tmaxMatchOffset = 1 << 15\n\tendBlockMarker = 256\n",
-             "two constants the decoder shares with the encoder, whose files (fast_encoder.go:44, huffman_bit_writer.go:20) are not translated"),
             (r"type ReadError = flate\.ReadError\n", "", "deprecated alias, never returned"),
             (r"type WriteError = flate\.WriteError\n", "", "likewise"),
             (r"CorruptInputError\(f\.roffset\)", "errCorrupt", "a CorruptInputError at any offset is the class CORRUPT"),
@@ -201,6 +216,39 @@ CFG = {
             (r"func NewReader\(r io\.Reader\)", "func NewReader(r flate.Reader)", "likewise"),
             (r"func \(z \*Reader\) Reset\(r io\.Reader\)", "func (z *Reader) Reset(r flate.Reader)", "likewise"),
             (r"z\.decompressor\.\(flate\.Resetter\)\.Reset", "z.decompressor.Reset", "the concrete type has the method"),
+        ],
+        # the write side.  sync.Pool is an allocation cache (a pooled bit writer is reset, pooled tokens are Reset: fresh ones are the same
+        # values); the debug branches under `debugDeflate` (false) are dropped by the translation itself, like the Go compiler does
+        "flate/stateless.go": [
+            (r"var bitWriterPool = sync\.Pool\{\n\tNew: func\(\) any \{\n\t\treturn newHuffmanBitWriter\(nil\)\n\t\},\n\}", "var bitWriterPool sync.Pool",
+             "sync.Pool is an allocation cache: Get is a fresh object (next patches), Put a no-op"),
+            (r"var tokensPool = sync\.Pool\{\n\tNew: func\(\) any \{\n\t\treturn &tokens\{\}\n\t\},\n\}", "var tokensPool sync.Pool", "likewise"),
+            (r"bitWriterPool\.Get\(\)\.\(\*huffmanBitWriter\)", "newHuffmanBitWriter(nil)", "what the pool's New returns"),
+            (r"tokensPool\.Get\(\)\.\(\*tokens\)", "&tokens{}", "what the pool's New returns"),
+            (r"func NewStatelessWriter\(dst io\.Writer\) io\.WriteCloser", "func NewStatelessWriter(dst io.Writer) *statelessWriter",
+             "the concrete type instead of io.WriteCloser (the driver calls Write and Close on it)"),
+        ],
+        "flate/huffman_bit_writer.go": [
+            (r'InternalError\("writeBytes with unfinished bits"\)', "errInternal", "the class `internal` (see flate/inflate.go)"),
+        ],
+        "flate/deflate.go": [
+            (r"\tcase level == NoCompression:\n.*?(\tcase level == ConstantCompression:\n)", r"\1", "init: the HuffmanOnly arm only (store, levels 1-9 and custom windows are not translated)"),
+            (r"\tcase level == DefaultCompression:\n.*?\tdefault:\n\t\treturn fmt\.Errorf\([^\n]*\)\n", '\tdefault:\n\t\treturn errors.New("flate: compression level not translated")\n', "likewise"),
+            (r"\(\*compressor\)\.fillBlock", "func(c *compressor, b []byte) int { return c.fillBlock(b) }", "a method expression spelt as the function it denotes"),
+            (r"\(\*compressor\)\.storeHuff", "func(c *compressor) { c.storeHuff() }", "likewise"),
+            (r"\t// We only need to reset a few things for Snappy\.\n\tif d\.fast != nil \{.*?\n\t\}\n", "", "reset: no fast encoder at this level"),
+            (r"\tdefault:\n\t\ts := d\.state\n.*?\t\ts\.maxInsertIndex = 0\n", "", "reset: the hash chains of levels 7-9"),
+            (r"\tif len\(w\.dict\) > 0 \{.*?\n\t\} else \{\n\t\t// w was created with NewWriter\n\t\tw\.d\.reset\(dst\)\n\t\}\n", "\tw.d.reset(dst)\n", "Writer.Reset: no NewWriterDict here (fillWindow is the match finders')"),
+        ],
+        "gzip/gzip.go": [
+            (r'\t"fmt"\n', '\t"encoding/binary"\n', "fmt only formats the message of an invalid level; the little-endian stores are spelt out (as in gzip/gunzip.go)"),
+            (r'fmt\.Errorf\("gzip: invalid compression level: %d", level\)', 'errors.New("gzip: invalid compression level")', "likewise"),
+            (r"\ble\.PutUint", "binary.LittleEndian.PutUint", "encoding/binary's little-endian stores"),
+            (r"\tHeader      // written at", "\tHdr Header  // written at", "the embedded Header as a named field (see gzip/gunzip.go)"),
+            (r"\t\tHeader: Header\{", "\t\tHdr: Header{", "likewise"),
+            (r"\bz\.(Extra|Name|Comment|OS)\b", r"z.Hdr.\1", "likewise"),
+            (r"uint32\(z\.ModTime\.Unix\(\)\)", "uint32(z.Hdr.ModTime)", "Header.ModTime is the integer the header holds (see gzip/gunzip.go)"),
+            (r"io\.WriteString\(z\.w, s\)", "z.w.Write([]byte(s))", "what io.WriteString does for a writer without WriteString"),
         ],
         "s2/hashtable_pool.go": [
             (r"= sync\.Pool\{New: func\(\) any \{ return &\w+\{\} \}\}", " sync.Pool",

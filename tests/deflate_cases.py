@@ -80,6 +80,57 @@ def block_of(kind, n, rng):
     raise ValueError(kind)
 
 
+def tie_mix(seed, n, every):
+    """Random bytes with every `every`-th byte an 'A': a little under 8 bits a byte, so that at a few hundred bytes the estimate of a
+    Huffman block lands on the stored size (tools/find_deflate_ties.py walks n for the exact tie)."""
+    b = bytearray(random.Random(0x71E5 + seed).randbytes(1024))
+    b[::every] = bytes([0x41]) * len(b[::every])
+    return bytes(b[:n])
+
+
+def tie_shift(seed, n, p):
+    """skewed() bytes whose heavy byte is 'h' for p sixteenths of them and 'a' for the rest: behind a block heavy in 'a' the cost under
+    its table grows with n until it meets the estimate of a new table."""
+    rng = random.Random(0x71E6 + seed)
+    return bytes(skewed(1, rng, ord("h") if rng.random() < p / 16 else ord("a"))[0] for _ in range(n))
+
+
+def tie_quick(delta):
+    """Two blocks of 2048 bytes over the bytes 32..255.  The second one's histogram is built, not searched: 32 byte values absent, 32
+    sixteen times, 192 eight times, so that the quick check's sum of (v - 8)^2 is 32*64 + 32*64 = 4096 = 2n exactly (`abs < max` is
+    false: the block goes on, and under the first block's table it is written as a Huffman block), and with a few counts moved by one,
+    4096 + delta for an even delta (the sum has the parity of the sum of the deviations, which is 0).  At 4094 the quick check stores."""
+    assert delta in (-2, 0, 2)
+    rng = random.Random(0x71E8)
+    first = []
+    for v in range(32, 64):
+        first += [v] * 28
+    for v in range(64, 256):
+        first += [v] * 6
+    counts = {v: 16 for v in range(32, 64)}
+    counts.update({v: 8 for v in range(64, 256)})
+    if delta == 2:
+        counts[64], counts[65] = 9, 7
+    elif delta == -2:  # 16 -> 15 and 8 -> 9: -15 + 1; six pairs 8 -> 9 / 7: + 12
+        counts[32], counts[64] = 15, 9
+        for k in range(6):
+            counts[66 + 2 * k], counts[67 + 2 * k] = 9, 7
+    second = [v for v, k in counts.items() for _ in range(k)]
+    assert len(first) == len(second) == 2048 and sum((k - 8) ** 2 for k in counts.values()) + 32 * 64 == 4096 + delta
+    rng.shuffle(first)
+    rng.shuffle(second)
+    return bytes(first) + bytes(second)
+
+
+def tie_first():
+    return block_of("skew-a", 2048, random.Random(0x71E7))
+
+
+# (margin name, value) -> generator arguments, found by `python tools/find_deflate_ties.py huff` with the model's margins
+TIES = {("ssize-est", 0): ("mix", 0, 481, 6), ("ssize-est", 1): ("mix", 0, 482, 6),
+        ("est-reuse", 0): ("shift", 0, 1597, 2), ("est-reuse", -1): ("shift", 0, 1605, 2)}
+
+
 def _fib_sum(k):
     a, b, s = 1, 1, 0
     for _ in range(k):
@@ -121,6 +172,14 @@ def directed():
     add("multi-huff-stored-huff", a1 + rng.randbytes(32768) + a2)
     add("multi-stored-first", rng.randbytes(32768) + text(40000, 5))
     add("multi-text-4", text(4 * 32768 + 17, 9))
+    # ties of writeBlockHuff and their neighbours, at blocks of 2048: ssize == estBits (stored wins) and one more; estBits == reuseSize
+    # (reuse wins) and one less (a new table behind the owed EOB)
+    for (name, m), (kind, seed, n, arg) in TIES.items():
+        data = tie_mix(seed, n, arg) if kind == "mix" else tie_first() + tie_shift(seed, n, arg)
+        add("tie-%s-%d" % (name, m), data, block=2048)
+    # the quick check's `abs < max` at abs == max - 2, max and max + 2 (float64 in the reference, integers in the model and the kernel)
+    for delta in (-2, 0, 2):
+        add("tie-abs-max%+d" % delta, tie_quick(delta), block=2048)
     return tuple(C)
 
 
@@ -151,6 +210,11 @@ def model(case, gzip=False):
     if not gzip:
         return res.data, res
     return M.gzip_deflate(data, block, penalty, end), res
+
+
+def emu_subset():
+    """What the emulator runs: every directed case and the first 160 seeded ones."""
+    return directed() + seeded()[:160]
 
 
 def totals(cases):

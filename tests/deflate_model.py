@@ -179,6 +179,7 @@ class BitWriter:
         self.codes = None
         self.counts = dict.fromkeys(DECISIONS, 0)
         self.boundary_phases = set()  # bit phases at which a block's codes ended
+        self.margins = []  # (decision, left side - right side) of every comparison taken between two encodings: what tools/find_deflate_ties.py reads
 
     @property
     def nbits(self):
@@ -242,6 +243,7 @@ class BitWriter:
         ssize = (n + 5) * 8
         if n > 1024:
             # float64 in the reference; exact in integers: sum (v - n/256)^2 < 2n  <=>  sum (256 v - n)^2 < 2 n 65536
+            self.margins.append(("abs-max", sum((256 * v - n) ** 2 for v in freq[:256]) - 2 * n * 65536))
             if sum((256 * v - n) ** 2 for v in freq[:256]) < 2 * n * 65536:
                 self.counts["quick-stored"] += 1
                 self.write_stored_header(n, eof)
@@ -255,6 +257,7 @@ class BitWriter:
             if self.last_header == 0:
                 est += 70 * 8
             est += est >> self.penalty
+        self.margins.append(("ssize-est", ssize - est))
         if ssize <= est:
             self.counts["est-stored"] += 1
             self.write_stored_header(n, eof)
@@ -263,6 +266,7 @@ class BitWriter:
         first = self.last_header == 0
         if self.last_header > 0:
             reuse = can_reuse_bits(self.lens, freq[:256])
+            self.margins.append(("est-reuse", est - reuse))
             if est < reuse:
                 self.counts["new-table-eob-owed"] += 1
                 if reuse == MAXI32:
@@ -307,6 +311,7 @@ class BitWriter:
 class Result:
     def __init__(self, data, counts, boundary_phases, end_phase):
         self.data, self.counts, self.boundary_phases, self.end_phase = data, counts, boundary_phases, end_phase
+        self.margins = []
 
 
 def deflate_ex(data, block=32768, penalty=10, end=END_CLOSE):
@@ -322,7 +327,9 @@ def deflate_ex(data, block=32768, penalty=10, end=END_CLOSE):
     end_phase = w.nbits
     w.write_stored_header(0, end == END_CLOSE)
     w.flush()
-    return Result(w.bytes(), w.counts, w.boundary_phases, end_phase)
+    res = Result(w.bytes(), w.counts, w.boundary_phases, end_phase)
+    res.margins = w.margins
+    return res
 
 
 def deflate(data, block=32768, penalty=10, end=END_CLOSE):

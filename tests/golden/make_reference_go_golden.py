@@ -40,6 +40,18 @@ def flate_main():
             f.write("flate.%s %s\n" % (name, FC.family_digest(cs, ref)))
 
 
+def deflate_main():
+    """tests/golden/reference_go_deflate_sha256.txt: one line `deflate.<family> <sha256>` per family of tests/deflate_ref_families.py, the
+    hash over the records (key, len, sha256(bytes)) of what the REFERENCE's DEFLATE writers give -- flate.NewWriter(w, HuffmanOnly), the
+    bare bit writer, StatelessDeflate, gzip's writer at both levels, EstimatedBits, translated (oracle_goref.flate_huffman_only ...).
+    Run alone with:  python tests/golden/make_reference_go_golden.py deflate      (half a minute)"""
+    import deflate_ref_families as F
+    ref = F.RefWriter()
+    with open(os.path.join(HERE, "reference_go_deflate_sha256.txt"), "w") as f:
+        for fam in F.FAMILIES:
+            f.write("deflate.%s %s\n" % (fam, F.digest(F.records(fam, ref))))
+
+
 def main():
     lines = {}
     dct = _lib.corpus_fill("T", DICT_SEED, 0, 1, 64 << 10).tobytes()
@@ -84,6 +96,10 @@ def main():
 
 
 if __name__ == "__main__":
-    if sys.argv[1:] != ["flate"]:
-        main()
-    flate_main()
+    if sys.argv[1:] == ["deflate"]:
+        deflate_main()
+    else:
+        if sys.argv[1:] != ["flate"]:
+            main()
+        flate_main()
+        deflate_main()

@@ -6,7 +6,9 @@ encode_best, encode_go), translated statement by statement into C++ at build tim
 slice and array semantics in oracle/ref_go/gort.h) and compiled here (oracle/Makefile `ref`).  It is built where /root/reference
 exists (this container) and travels to the GPU box as a built file; nothing of the reference is stored in the repository.
 The portable flavour also holds the reference's inflate and gunzip (flate/inflate.go, inflate_gen.go, dict_decoder.go, gzip/gunzip.go):
-flate_inflate / gunzip below, the judge of tests/flate_model.py."""
+flate_inflate / gunzip below, the judge of tests/flate_model.py — and the reference's two DEFLATE writers without match finder state
+(flate/huffman_bit_writer.go, huffman_code.go, token.go, stateless.go, the HuffmanOnly part of deflate.go, gzip/gzip.go): flate_stateless,
+flate_huffman_only, gzip_write ... below, the judge of tests/deflate_model.py and tests/stateless_model.py."""
 import ctypes as C
 import os
 import subprocess
@@ -97,6 +99,21 @@ def lib():
         if hasattr(L, "goref_gunzip"):
             L.goref_gunzip.restype = C.c_longlong
             L.goref_gunzip.argtypes = [C.c_char_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+        if hasattr(L, "goref_flate_stateless"):
+            L.goref_flate_stateless.restype = C.c_longlong
+            L.goref_flate_stateless.argtypes = [C.c_char_p, C.c_longlong, C.c_int, C.c_char_p, C.c_longlong, C.c_void_p, C.c_longlong]
+            L.goref_flate_stateless_writer.restype = C.c_longlong
+            L.goref_flate_stateless_writer.argtypes = [C.c_char_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong]
+            L.goref_flate_huffman_only.restype = C.c_longlong
+            L.goref_flate_huffman_only.argtypes = [C.c_char_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong]
+            L.goref_flate_block_huff.restype = C.c_longlong
+            L.goref_flate_block_huff.argtypes = [C.c_char_p, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_longlong]
+            L.goref_flate_block_dynamic.restype = C.c_longlong
+            L.goref_flate_block_dynamic.argtypes = [C.c_void_p, C.c_longlong, C.c_char_p, C.c_longlong, C.c_int, C.c_void_p, C.c_longlong]
+            L.goref_flate_estimated_bits.restype = C.c_longlong
+            L.goref_flate_estimated_bits.argtypes = [C.c_void_p, C.c_longlong]
+            L.goref_gzip_write.restype = C.c_longlong
+            L.goref_gzip_write.argtypes = [C.c_int, C.c_char_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong]
         _libs[key] = L
     if key == "amd64":
         L.goref_force_bmi(0 if _flavour == "amd64-nobmi" else -1)
@@ -359,3 +376,99 @@ def gunzip(data: bytes, multistream=True, want_header=False, max_out: int = 1 <<
         fields["Extra"] = parts[0] if has_extra else None
         fields["Name"], fields["Comment"] = parts[1].decode("utf-8"), parts[2].decode("utf-8")
     return res + (fields,)
+
+
+def deflate_available():
+    """The library is there and has the reference's DEFLATE writers in it."""
+    return available() and hasattr(lib(), "goref_flate_stateless")
+
+
+WRITE_FLUSH, WRITE_CLOSE = -1, -2   # ops of flate_huffman_only / gzip_write; an op >= 0 is Write(data[end of the Write before:op])
+GZIP_HUFFMAN_ONLY, GZIP_STATELESS = -2, -3
+
+
+def _written(n, out, what):
+    if n < 0:
+        raise ValueError("%s: %d (-1 a panic, -2 the output is too small, -5 the reference returned an error)" % (what, n))
+    return out.raw[:n]
+
+
+def _cap(n, blocks):
+    return n + 200 * blocks + 64
+
+
+def _i64(vals):
+    vals = [int(v) for v in vals]
+    return (C.c_longlong * max(1, len(vals)))(*vals), len(vals)
+
+
+def _u32(vals):
+    vals = [int(v) for v in vals]
+    return (C.c_uint32 * max(1, len(vals)))(*vals), len(vals)
+
+
+def flate_stateless(data: bytes, eof=True, dict: bytes = b"") -> bytes:
+    """flate.StatelessDeflate(w, data, eof, dict) of the reference: what w received."""
+    data, dict = bytes(data), bytes(dict)
+    cap = _cap(len(data), len(data) // 24575 + 2)
+    out = C.create_string_buffer(cap)
+    return _written(lib().goref_flate_stateless(data, len(data), int(bool(eof)), dict or None, len(dict), out, cap), out, "goref_flate_stateless")
+
+
+def flate_stateless_writer(data: bytes, cuts) -> bytes:
+    """w := flate.NewStatelessWriter(dst); Write(data[prev:cut]) for every cut; Close()."""
+    data = bytes(data)
+    arr, k = _i64(cuts)
+    cap = _cap(len(data), len(data) // 24575 + 2 * k + 2)
+    out = C.create_string_buffer(cap)
+    return _written(lib().goref_flate_stateless_writer(data, len(data), arr, k, out, cap), out, "goref_flate_stateless_writer")
+
+
+def flate_huffman_only(data: bytes, ops) -> bytes:
+    """w, _ := flate.NewWriter(dst, flate.HuffmanOnly), then `ops` in order: n >= 0 Write(data[prev:n]), WRITE_FLUSH Flush(), WRITE_CLOSE Close()."""
+    data = bytes(data)
+    arr, k = _i64(ops)
+    cap = _cap(len(data), len(data) // 32768 + 2 * k + 2)
+    out = C.create_string_buffer(cap)
+    return _written(lib().goref_flate_huffman_only(data, len(data), arr, k, out, cap), out, "goref_flate_huffman_only")
+
+
+BLOCK_HUFF_CLOSE, BLOCK_HUFF_FLUSH, BLOCK_HUFF_BARE = 0, 1, 2
+
+
+def flate_block_huff(data: bytes, block: int, penalty: int, end: int) -> bytes:
+    """A bare newHuffmanBitWriter with logNewTablePenalty = penalty: writeBlockHuff(false, chunk, false) per full block of `block` bytes that
+    more input follows, writeBlockHuff(false, rest, true) for the rest; then what close (BLOCK_HUFF_CLOSE) or syncFlush (BLOCK_HUFF_FLUSH)
+    write behind their last block, or flush alone (BLOCK_HUFF_BARE: the reference's own test of writeBlockHuff)."""
+    data = bytes(data)
+    cap = _cap(len(data), len(data) // max(1, block) + 2)
+    out = C.create_string_buffer(cap)
+    return _written(lib().goref_flate_block_huff(data, len(data), int(block), int(penalty), int(end), out, cap), out, "goref_flate_block_huff")
+
+
+def flate_block_dynamic(tokens, data, sync: bool) -> bytes:
+    """tokens := indexTokens(tokens); a fresh newHuffmanBitWriter: writeBlockDynamic(&tokens, false, data, sync); flush -- the reference's own
+    TestWriteBlockDynamic / ...Sync.  A token is the reference's word (stateless_model.Tokens.tok without an EOB); data None: a nil input."""
+    arr, k = _u32(tokens)
+    n = 0 if data is None else len(data)
+    cap = _cap(n + 4 * k, 4)
+    out = C.create_string_buffer(cap)
+    return _written(lib().goref_flate_block_dynamic(arr, k, None if data is None else bytes(data), n, int(bool(sync)), out, cap), out, "goref_flate_block_dynamic")
+
+
+def flate_estimated_bits(tokens) -> int:
+    """indexTokens(tokens).EstimatedBits() of the reference (token.go)."""
+    arr, k = _u32(tokens)
+    n = int(lib().goref_flate_estimated_bits(arr, k))
+    if n < 0:
+        raise ValueError("goref_flate_estimated_bits: %d" % n)
+    return n
+
+
+def gzip_write(level: int, data: bytes, ops) -> bytes:
+    """z, _ := gzip.NewWriterLevel(dst, level) for GZIP_HUFFMAN_ONLY or GZIP_STATELESS, then `ops` as in flate_huffman_only."""
+    data = bytes(data)
+    arr, k = _i64(ops)
+    cap = _cap(len(data), len(data) // 24575 + 2 * k + 4)
+    out = C.create_string_buffer(cap)
+    return _written(lib().goref_gzip_write(int(level), data, len(data), arr, k, out, cap), out, "goref_gzip_write")

@@ -37,6 +37,29 @@ def _plant(b, rng, every, length):
     return b
 
 
+def tie_planted(seed):
+    """Random bytes with planted matches of a seeded length, spacing and size: tools/find_deflate_ties.py walks the seeds for inputs
+    whose token count lands on len - len>>4 (the last count that still goes to writeBlockDynamic) and on one more (writeBlockHuff)."""
+    rng = random.Random(0x57A7 + seed)
+    n = rng.randrange(40, 2500)
+    return planted(n, rng, rng.choice((24, 32, 40, 48, 64)), rng.choice((5, 6, 7, 8)))
+
+
+TOKEN_TIES = {0: (73, 174, 233, 235), 1: (32, 111, 320, 333)}   # tokens - (len - len>>4) -> seeds of tie_planted
+
+
+# newSize - reuseSize of the second, open block of shifted_alphabet(seed)[:FIRST + m] -> (seed, m): reuse wins at 0 and 1, the new table at
+# -1 and -2.  newSize is 2 * (lastHeader + EstimatedBits) + the EOB's length, so each of them is one bit of EstimatedBits from the other side.
+DYN_TIES = {1: ((0, 506), (6, 491)), 0: ((0, 508), (2, 457)), -1: ((3, 592), (6, 492)), -2: ((2, 463), (4, 565))}
+STORED_BY_SIZE = (0, 1, 2, 3, 5, 6, 7, 9)   # seeds of stored_by_size_planted at which the dynamic block would be larger than the bytes
+NEW_TABLE_SEEDS = (5, 6, 7, 9, 10, 11, 13, 14)   # shifted_alphabet seeds whose second, open block takes the new table
+
+
+def stored_by_size_planted(seed):
+    rng = random.Random(0xD5B0 + seed)
+    return planted(rng.randrange(200, 700), rng, 40, 6)
+
+
 def shifted_alphabet(seed):
     """Block 1: 32 symbols at geometric frequencies (ratio 0.8), every one of them a literal somewhere, with planted matches; blocks 2
     and 3: the sixteen rarest at equal frequencies, matches planted the same way.  Block 2 can be written under block 1's table, at
@@ -49,6 +72,35 @@ def shifted_alphabet(seed):
     b1 = _plant(b1, rng, 100, 12)
     b2 = _plant(bytearray(rng.choices(syms[16:], k=LATER)), rng, 100, 12)
     return bytes(b1) + bytes(b2) + bytes(b2[:2000])
+
+
+def huff_block(n, rng, history=b"", first=0x30):
+    """A block that writeBlockHuff writes as a Huffman block: 24 symbols at geometric frequencies (ratio 0.75, about 3.3 bits a byte, so
+    that even the DOUBLED estimate of this path stays below the stored size) in which statelessEnc finds one match, planted at byte 16,
+    and no other.  Such bytes repeat their 4-byte strings all the time, so the model's own match finder is run over the block (behind
+    `history`, the 8 KiB the reference keeps in front of a later block) and a byte inside every match it finds is drawn again, until
+    none is left.  A prefix of the block has the same property."""
+    syms = list(range(first, first + 24))
+    wts = [0.75 ** i for i in range(24)]
+    b = bytearray(rng.choices(syms, weights=wts, k=n))
+    b[16:24] = b[0:8]
+    h = len(history)
+    for _ in range(1000):
+        t = M.Tokens()
+        M.stateless_enc(t, history + bytes(b), h)
+        ev = [e for e in t.events if e[0] - h >= 32]
+        if not ev:
+            return bytes(b)
+        for s, _, back, _, _ in ev:
+            i = s - h + back + 1
+            old = b[i]
+            while b[i] == old:
+                b[i] = rng.choices(syms, weights=wts)[0]
+    raise AssertionError("huff_block: matches left")
+
+
+# inputs whose LAST block is Huffman-only and goes on under the table in force: with eof the stream has no final block
+NO_FINAL_BLOCK = ("huff-reuse-2-eof", "huff-reuse-2-short-tail-eof")
 
 
 def pieces(spec, rng):
@@ -167,6 +219,46 @@ def directed():
     add("match-into-dict-beyond-8192", text(8193, 123)[:60] + text(100, 9), True, text(8193, 123))
     add("dict-random-input", rand(3000, rng), False, text(4000, 5))
     add("dict-text-two-blocks", text(FIRST + 500, 70000), True, text(6000, 64000))
+    # writeBlockHuff that WRITES a Huffman block, and the blocks behind it: under the table in force (with eof: no final block at all;
+    # open: the EOB and the empty stored block), a third block that goes on to writeBlockDynamic (lastHuffMan: the owed EOB, a new
+    # table), another alphabet (a symbol the table lacks: MaxInt32, a new table), random bytes (stored behind the owed EOB)
+    rng = random.Random(0x4AFF0E0B)
+    w1 = huff_block(FIRST, rng)
+    w2 = huff_block(LATER, rng, w1[-M.MAX_DICT:])
+    add("huff-reuse-2-eof", w1 + w2)
+    add("huff-reuse-2-short-tail-eof", w1 + w2[:3000])
+    add("huff-reuse-2-open", w1 + w2[:3500], False)
+    add("huff-one-block-eof", w1[:20000])
+    add("huff-one-block-open", w1[:1500], False)
+    add("huff-huff-then-dynamic", w1 + w2 + text(3000, 41))
+    add("huff-then-dynamic", w1 + text(3500, 43), False)
+    add("huff-then-other-alphabet", w1 + huff_block(3800, rng, w1[-M.MAX_DICT:], first=0x80))
+    add("huff-reuse-then-other-alphabet", w1 + w2 + huff_block(2600, rng, w2[-M.MAX_DICT:], first=0x80), False)
+    add("huff-then-random", w1 + rand(3000, rng))
+    add("huff-then-short-fixed", w1 + (text(5, 3) * 30)[:100])
+    t1 = text(FIRST, 47)
+    add("dynamic-then-huff", t1 + huff_block(3900, rng, t1[-M.MAX_DICT:]))
+    # reuse of a dynamic table, the new table with its owed EOB, and stored-by-size, in two-block inputs the emulator runs too
+    for k in range(4):
+        add("text-text-reuse-%d" % k, text(FIRST + 2500 + 300 * k, 7000 * k + 13), k % 2 == 0)
+    # (seeds found by `python tools/find_deflate_ties.py shapes`: the model decides for the new table in the second, open block; with eof the
+    # last block never weighs reuse)
+    for seed in NEW_TABLE_SEEDS:
+        add("shifted-alphabet-two-blocks-%d" % seed, shifted_alphabet(seed)[:FIRST + 3900], False)
+    for k in range(5):
+        add("dense-then-dense-%d" % k, planted(FIRST + 1500 + 500 * k, rng, 100, 12), k % 2 == 1)
+    # a few hundred random bytes with matches planted: just under 15/16 tokens, and the dynamic block would be larger than the bytes
+    for seed in STORED_BY_SIZE:
+        d = stored_by_size_planted(seed)
+        add("planted-stored-by-size-%d" % len(d), d, seed % 2 == 0)
+    # writeBlockDynamic's reuse against the doubled estimate of a new table, within two bits either way
+    for m, pairs in DYN_TIES.items():
+        for seed, extra in pairs:
+            add("tie-dyn-new-reuse%+d-seed-%d" % (m, seed), shifted_alphabet(seed)[:FIRST + extra], False)
+    # the token count on the threshold between writeBlockDynamic and writeBlockHuff, and one above it
+    for m, seeds in TOKEN_TIES.items():
+        for seed in seeds:
+            add("tie-tokens-%d-seed-%d" % (m, seed), tie_planted(seed), seed % 2 == 0)
     names = [x[0] for x in c]
     assert len(set(names)) == len(names)
     return tuple(c)
@@ -239,7 +331,7 @@ def total_counts(cases=None):
 
 def emu_subset():
     """What the emulator runs: every directed case of at most two blocks, a few of more, and every sixth seeded one."""
-    d = [c for c in directed() if len(c[1]) <= FIRST + 4000 or c[0].startswith(("alt-text-other", "alt-other-text", "shifted-alphabet-0", "alt-skew-skew", "alt-text-planted-"))]
+    d = [c for c in directed() if len(c[1]) <= FIRST + 4000 or c[0].startswith(("alt-text-other", "alt-other-text", "shifted-alphabet-0", "alt-skew-skew", "alt-text-planted-", "huff-"))]
     return tuple(d) + seeded()[::6]
 
 

@@ -106,7 +106,7 @@ class Tokens:
         bits = 0
         n_matches = 0
         total = self.n
-        at_least_one = lambda v: F32(1) if v < 1 else v  # noqa: E731
+        at_least_one = lambda v: F32(1) if v < 1 else F32(15) if v > 15 else v  # noqa: E731  (huffman_code.go:374-382)
         if total > 0:
             inv = F32(F32(1.0) / F32(total))
             for v in self.lit_hist:
@@ -361,6 +361,7 @@ class Writer(BitWriter):
             new_size = self.last_header + t.estimated_bits()
             new_size += self.lens[256] + (new_size >> self.penalty)
             reuse = bit_length(self.lens, lit_freq) + bit_length(self.olens, off_freq) + extra
+            self.margins.append(("dyn-new-reuse", new_size - reuse))
             if new_size < reuse:
                 self.counts["dyn-new-table-eob-owed"] += 1
                 self._owed_eob()
@@ -421,6 +422,7 @@ class Writer(BitWriter):
 class Result:
     def __init__(self, data, counts, blocks):
         self.data, self.counts, self.blocks = data, counts, blocks
+        self.margins = []
 
 
 def block_cuts(n, dict_len):
@@ -462,15 +464,19 @@ def stateless_deflate_ex(data, eof=True, dict=b""):
             w.write_stored_header(len(unc), is_eof)
             w.write_bytes(unc)
         elif t.n > len(unc) - (len(unc) >> 4):
+            w.margins.append(("tokens-15/16", t.n - (len(unc) - (len(unc) >> 4))))
             w.counts["huffman-only"] += 1
             w.write_block_huff(is_eof, unc, last)
         else:
+            w.margins.append(("tokens-15/16", t.n - (len(unc) - (len(unc) >> 4))))
             w.write_block_dynamic(t, is_eof, unc, last)
         blocks.append(t)
     if not eof:
         w.write_stored_header(0, False)
     w.flush()
-    return Result(w.bytes(), w.counts, blocks)
+    res = Result(w.bytes(), w.counts, blocks)
+    res.margins = w.margins
+    return res
 
 
 def stateless_deflate(data, eof=True, dict=b""):

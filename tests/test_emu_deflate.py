@@ -11,7 +11,7 @@ import deflate_model as M
 import emu_lib
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES = D.directed() + D.seeded()[:160]
+CASES = D.emu_subset()
 GROUPS = D.groups(CASES)
 
 

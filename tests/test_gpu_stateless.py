@@ -127,7 +127,13 @@ def test_device_inflates_what_it_wrote(kclib):
         cs = GROUPS[key]
         src, off = D.pack([c[1] for c in cs])
         outs = flate.StatelessDeflateAll(src, off, True, key[1])
-        assert flate.InflateAll(*pack(outs), dict=key[1] or None) == [c[1] for c in cs]
+        back = flate.InflateAll(*pack(outs), dict=key[1] or None)
+        for c, got in zip(cs, back):
+            if c[0] in S.NO_FINAL_BLOCK:   # a stream without a final block, as the reference writes it: the input ends inside the stream
+                assert isinstance(got, flate.ErrUnexpectedEOF), c[0]
+            else:
+                assert got == c[1], c[0]
+        assert key[1] or sum(c[0] in S.NO_FINAL_BLOCK for c in cs) == len(S.NO_FINAL_BLOCK)
     cs = GROUPS[(True, b"")][::2]
     src, off = D.pack([c[1] for c in cs])
     outs = gzip.GzipAll(src, off, gzip.StatelessCompression)
